@@ -37,9 +37,17 @@ sides hash-partitioned by the join key and exchanged over RCCL all-to-all
 (shuffle join, partition.rs:151-212), local fused join + partial aggregate,
 partial/final by group key.  Runs through a world-1 RCCL group at N = 1.
 
-After the timed steps the result is checked at the full size: Σ COUNT over the
-groups equals the device filter's count of x > 49, Σ SUM(v) equals the
-device's filtered Σ v (1e-6), and every group is present.
+A plain run sets up, warms up, times the steps and prints the result line.
+--dump-outputs DIR then also writes what the last timed step returned (the
+group keys and the aggregates a caller receives) as DIR/<name>.npy in float64,
+rows ordered by group key; the inputs come from a fixed seed, so two builds run
+with the same arguments can be compared output for output.
+
+--full adds what the headline figure does not need.  After the timed steps the
+result is checked at the full size: Σ COUNT over the groups equals the device
+filter's count of x > 49, Σ SUM(v) equals the device's filtered Σ v (1e-6),
+and every group is present.  Then the same query runs on the host CPU
+(cpu_baseline, N = 1 only).
 """
 from __future__ import annotations
 
@@ -76,7 +84,14 @@ def parse():
     ap.add_argument("--cpu-sample-mt", type=int, default=400_000_000, help="fact rows for the all-cores CPU baseline")
     ap.add_argument("--traffic-json", default=os.path.join(ROOT, "profiles", "traffic_latest.json"),
                     help="PMC-derived HBM bytes per launch of the probe kernel (tools/pmc_traffic.py)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also check the result at the full size after the timed steps and run the CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float64, rows ordered by group key)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def cpu_model() -> str:
@@ -155,6 +170,37 @@ def cpu_baseline(args):
     return out
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(res, agg_names, outdir, rank, world):
+    """What the step returned (group-key columns, aggregate columns) as outdir/<name>.npy in float64,
+    rows ordered by the group key (GROUP BY promises no row order; the ordering makes two runs
+    comparable element for element).  A column with NULLs also gets <name>_valid.npy (1.0 = valid).
+    At N > 1 every rank writes the groups it owns, as <name>.rank<r>.npy."""
+    gk, ga, _ = res
+    keys = [c.to_numpy() for c in gk]
+    cols = keys + [c.to_numpy() for c in ga]
+    by = []  # np.lexsort: the last entry is the most significant
+    for vals, valid in reversed(keys):
+        by.append(vals)
+        if valid is not None:
+            by.append(valid)
+    order = np.lexsort(by) if by else slice(None)
+    names = [f"group_key_{i}" for i in range(len(keys))] + list(agg_names)
+    suffix = f".rank{rank}" if world > 1 else ""
+    out = {}
+    for name, (vals, valid) in zip(names, cols):
+        out[name] = np.ascontiguousarray(np.asarray(vals)[order], dtype=np.float64)
+        if valid is not None:
+            out[name + "_valid"] = np.ascontiguousarray(np.asarray(valid)[order], dtype=np.float64)
+    total = sum(a.nbytes for a in out.values())
+    assert total <= DUMP_MAX_BYTES, f"--dump-outputs: {total} bytes of results, the limit is {DUMP_MAX_BYTES}"
+    os.makedirs(outdir, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(outdir, f"{name}{suffix}.npy"), a)
+
+
 def torch_device_count():
     import torch
     return torch.cuda.device_count()
@@ -209,7 +255,9 @@ def main():
         sys.exit(subprocess.run(spawn_command(sys.argv[1:], args.gpus, free_port()), env=env).returncode)
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if os.environ.get("QEH_BENCH_LAUNCH_PROBE"):  # (tests/test_bench_launch.py: the rank's view, no GPU work)
-        print(json.dumps({"rank": int(os.environ.get("RANK", "0")), "world": world, "gpus": args.gpus}), flush=True)
+        # one write per rank: the ranks share the launcher's pipe, and a line written in pieces can interleave
+        sys.stdout.write(json.dumps({"rank": int(os.environ.get("RANK", "0")), "world": world, "gpus": args.gpus}) + "\n")
+        sys.stdout.flush()
         return
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -318,32 +366,37 @@ def main():
         tdist.all_reduce(t, op=tdist.ReduceOp.MAX)
         elapsed = float(t.item())
 
-    # result checks at the full size (size-independent properties): every selected fact row
-    # landed in exactly one group (Σ COUNT = rows with x > threshold, counted independently on
-    # the device by the filter operator), and Σ SUM(v) over the groups = the filtered Σ v
-    gk, ga, g = res
-    counts, _ = ga[1].to_numpy()
-    sums, _ = ga[0].to_numpy()
-    counted, groups, vsum = int(counts.sum()), int(g), float(sums.sum())
-    if rehearse:  # the local operator over the same fact rows and dim shard
-        _, lga, lg = ctx.join_filter_aggregate([x, k, v], 1, pred, dk, [dg], aggs)
-        want_rows, want_sum = int(lga[1].to_numpy()[0].sum()), float(lga[0].to_numpy()[0].sum())
-        assert int(lg) == groups, f"{groups} groups, the local operator {int(lg)}"
-        args.groups = groups  # every group of the shard, checked against the local operator above
-    else:
-        fx, want_rows = ctx.filter([x, v], pred, out_idx=[1])
-        _, want_sum_cols, _ = ctx.hash_aggregate([], fx, [(AF.Sum, 0)])
-        want_sum = float(want_sum_cols[0].to_numpy()[0][0]) if want_rows else 0.0
-    if dist:
-        t = torch.tensor([counted, groups, want_rows], device=cdev, dtype=torch.int64)
-        tdist.all_reduce(t)
-        counted, groups, want_rows = (int(q) for q in t.tolist())
-        t = torch.tensor([vsum, want_sum], device=cdev, dtype=torch.float64)
-        tdist.all_reduce(t)
-        vsum, want_sum = (float(q) for q in t.tolist())
-    assert counted == want_rows, f"Σ COUNT over groups {counted} != rows passing the filter {want_rows}"
-    assert abs(vsum - want_sum) <= 1e-6 * max(abs(want_sum), 1e-300), f"Σ SUM(v) {vsum} != filtered Σ v {want_sum}"
-    assert groups == args.groups, f"{groups} groups, expected {args.groups}"
+    if args.dump_outputs:
+        dump_outputs(res, ["sum_v", "count_v"], args.dump_outputs, rank, world)
+
+    counted = groups = None
+    if args.full:
+        # result checks at the full size (size-independent properties): every selected fact row
+        # landed in exactly one group (Σ COUNT = rows with x > threshold, counted independently on
+        # the device by the filter operator), and Σ SUM(v) over the groups = the filtered Σ v
+        gk, ga, g = res
+        counts, _ = ga[1].to_numpy()
+        sums, _ = ga[0].to_numpy()
+        counted, groups, vsum = int(counts.sum()), int(g), float(sums.sum())
+        if rehearse:  # the local operator over the same fact rows and dim shard
+            _, lga, lg = ctx.join_filter_aggregate([x, k, v], 1, pred, dk, [dg], aggs)
+            want_rows, want_sum = int(lga[1].to_numpy()[0].sum()), float(lga[0].to_numpy()[0].sum())
+            assert int(lg) == groups, f"{groups} groups, the local operator {int(lg)}"
+            args.groups = groups  # every group of the shard, checked against the local operator above
+        else:
+            fx, want_rows = ctx.filter([x, v], pred, out_idx=[1])
+            _, want_sum_cols, _ = ctx.hash_aggregate([], fx, [(AF.Sum, 0)])
+            want_sum = float(want_sum_cols[0].to_numpy()[0][0]) if want_rows else 0.0
+        if dist:
+            t = torch.tensor([counted, groups, want_rows], device=cdev, dtype=torch.int64)
+            tdist.all_reduce(t)
+            counted, groups, want_rows = (int(q) for q in t.tolist())
+            t = torch.tensor([vsum, want_sum], device=cdev, dtype=torch.float64)
+            tdist.all_reduce(t)
+            vsum, want_sum = (float(q) for q in t.tolist())
+        assert counted == want_rows, f"Σ COUNT over groups {counted} != rows passing the filter {want_rows}"
+        assert abs(vsum - want_sum) <= 1e-6 * max(abs(want_sum), 1e-300), f"Σ SUM(v) {vsum} != filtered Σ v {want_sum}"
+        assert groups == args.groups, f"{groups} groups, expected {args.groups}"
 
     ms_per_step = elapsed * 1e3 / args.steps
     value = total_rows * args.steps / elapsed
@@ -391,7 +444,7 @@ def main():
             traffic = None
 
     if rank == 0:
-        cpu = cpu_baseline(args) if world == 1 and not cfg4 and not rehearse else None  # an N=1 figure
+        cpu = cpu_baseline(args) if args.full and world == 1 and not cfg4 and not rehearse else None  # an N=1 figure
         if cfg4:
             workload = ("BASELINE config 4: hash-partitioned join + aggregate (filter f.x > 49, both sides "
                         "hash-partitioned by the join key over RCCL all-to-all, local fused join + partial "
@@ -457,7 +510,8 @@ def main():
             "dist_final": getattr(dx, "last_final", None) if dx is not None else None,
             "result_groups": groups,
             "result_rows_counted": counted,
-            "result_check": ("Σ COUNT, Σ SUM(v) (1e-6) and groups == the local operator over the same dim shard: passed"
+            "result_check": ("not run (--full checks the result)" if not args.full else
+                             "Σ COUNT, Σ SUM(v) (1e-6) and groups == the local operator over the same dim shard: passed"
                              if rehearse else
                              "Σ COUNT == device filter count, Σ SUM(v) == device filtered Σ v (1e-6), groups == "
                              f"{args.groups}: passed"),
