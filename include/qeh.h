@@ -209,7 +209,10 @@ int qeh_expr_type(const int32_t *col_dtypes, int n_cols, const qeh_expr *expr, i
  * n_keys >= 1: one row per distinct key tuple (NULL keys form one group);
  * out_keys[n_keys], out_aggs[n_aggs] are filled; row order unspecified.
  * Result types follow operators.rs:745-848 (COUNT Int64; SUM int->Int64,
- * float->Float64; AVG Float64; MIN/MAX keep the input type).              */
+ * float->Float64; AVG Float64; MIN/MAX keep the input type).
+ * Utf8 keys are grouped by their dictionary codes (qeh_utf8_dict_encode) and come back as Utf8
+ * columns; Utf8 aggregate inputs (MIN / MAX of strings) are QEH_E_UNSUPPORTED.  The same holds
+ * for qeh_filter_aggregate and for the build-side group keys of qeh_join_filter_aggregate. */
 int qeh_hash_aggregate(qeh_ctx *ctx, const qeh_column *keys, int n_keys,
                        const qeh_column *agg_inputs, int n_inputs, const qeh_agg *aggs,
                        int n_aggs, int64_t input_batches, qeh_column *out_keys,
@@ -433,9 +436,21 @@ int qeh_dense_states_take_status(qeh_ctx *ctx, const double *in, int n_vals, int
 int qeh_fused_items_check(qeh_ctx *ctx, const qeh_column *probe_cols, int n_probe_cols, int probe_key_idx,
                           const qeh_expr *predicate, const qeh_agg *aggs, int n_aggs);
 
+/* Order-preserving dictionary encoding of a Utf8 column.
+ * codes[i] = index of row i's string in `dict`; dict holds the column's distinct non-NULL
+ * strings in strictly ascending byte-wise (unsigned) lexicographic order, so
+ * codes compare exactly as the strings do (arrow's order on StringArray, the order
+ * k_utf8_cmp uses).  out_codes: INT32, length n, validity = the input's (NULL rows keep a
+ * cleared bit, value 0); out_dict: UTF8, D rows, no NULLs.  The empty string is a value,
+ * distinct from NULL.  Honours col->offset.  n == 0 or all-NULL -> D == 0.
+ * D > INT32_MAX -> QEH_E_UNSUPPORTED.  The sort, aggregate and window entry points below use
+ * it for their Utf8 key columns (one dictionary per column). */
+int qeh_utf8_dict_encode(qeh_ctx *ctx, const qeh_column *col, qeh_column *out_codes, qeh_column *out_dict);
+
 /* Stable lexicographic sort -> permutation (UINT32 row ids) of the input.
  * Intended semantics of `Sort` (physical_plan.rs:40-44; executor.rs:290-297
- * is the identity): per-key ascending flag, NULLs first, floats totalOrder. */
+ * is the identity): per-key ascending flag, NULLs first, floats totalOrder,
+ * Utf8 keys in byte-wise lexicographic order (sorted by their dictionary codes). */
 int qeh_sort_indices(qeh_ctx *ctx, const qeh_column *keys, int n_keys, const int8_t *ascending,
                      qeh_column *out_perm);
 
@@ -463,7 +478,8 @@ int qeh_take(qeh_ctx *ctx, const qeh_column *col, const qeh_column *indices, qeh
 /* ROW_NUMBER() OVER (PARTITION BY part_keys ORDER BY order_keys): Int64 column
  * aligned to input order; 1-based within each partition, ties broken by input
  * position (docs/WINDOW_FUNCTIONS.md:44-65; `WindowFunctionType::RowNumber`,
- * physical_plan.rs:160-179). */
+ * physical_plan.rs:160-179).  Utf8 PARTITION BY / ORDER BY keys go through their dictionary
+ * codes, here and in qeh_window. */
 int qeh_row_number(qeh_ctx *ctx, const qeh_column *part_keys, int n_part,
                    const qeh_column *order_keys, int n_order, const int8_t *ascending,
                    qeh_column *out_rn);
@@ -476,7 +492,8 @@ int qeh_row_number(qeh_ctx *ctx, const qeh_column *part_keys, int n_part,
  *   LAG / LEAD(arg, param >= 0 rows) / FIRST_VALUE / LAST_VALUE(arg) -> arg's type
  *   (Int32/Int64/Float32/Float64), NULL where arg is NULL or the offset leaves the partition
  *   (then *dflt, the value's bit pattern, when dflt != NULL).  LAST_VALUE spans the whole
- *   partition (WindowExpr carries no frame).  Peers compare keys by value bits (NULLs equal).
+ *   partition (WindowExpr carries no frame).  Peers compare keys by value bits (NULLs equal;
+ *   Utf8 keys by their dictionary codes).  A Utf8 `arg` is QEH_E_UNSUPPORTED.
  * With no keys (OVER ()), `arg` must be given and supplies the row count. */
 int qeh_window(qeh_ctx *ctx, int32_t func, const qeh_column *part_keys, int n_part,
                const qeh_column *order_keys, int n_order, const int8_t *ascending,

@@ -3733,10 +3733,10 @@ static int aggregate_rows(qeh_ctx *ctx, int gm, const ColSet &cols, int64_t n, c
     return QEH_OK;
 }
 
-int hash_aggregate_filtered(qeh_ctx *ctx, const qeh_column *keys, int n_keys, const qeh_column *agg_inputs,
-                            int n_inputs, const qeh_agg *aggs, int n_aggs, const qeh_column *pred_cols,
-                            int n_pred_cols, const qeh_expr *predicate, int64_t input_batches,
-                            qeh_column *out_keys, qeh_column *out_aggs, int64_t *out_groups);
+static int hash_aggregate_coded(qeh_ctx *ctx, const qeh_column *keys, int n_keys, const qeh_column *agg_inputs,
+                                int n_inputs, const qeh_agg *aggs, int n_aggs, const qeh_column *pred_cols,
+                                int n_pred_cols, const qeh_expr *predicate, int64_t input_batches,
+                                qeh_column *out_keys, qeh_column *out_aggs, int64_t *out_groups);
 
 // More aggregates than one kernel carries (kMaxAggs): run the operator once per
 // chunk of aggregates.  Group order differs between runs (slot races), so every
@@ -3756,8 +3756,8 @@ static int aggregate_chunked(qeh_ctx *ctx, const qeh_column *keys, int n_keys, c
     for (int a0 = 0; a0 < n_aggs; a0 += kMaxAggs) {
         const int na = std::min(kMaxAggs, n_aggs - a0);
         int64_t g = 0;
-        int s = hash_aggregate_filtered(ctx, keys, n_keys, agg_inputs, n_inputs, aggs + a0, na, pred_cols,
-                                        n_pred_cols, predicate, input_batches, ck.data(), out_aggs + a0, &g);
+        int s = hash_aggregate_coded(ctx, keys, n_keys, agg_inputs, n_inputs, aggs + a0, na, pred_cols,
+                                     n_pred_cols, predicate, input_batches, ck.data(), out_aggs + a0, &g);
         if (s != QEH_OK) {
             release_all();
             return s;
@@ -3797,12 +3797,11 @@ static int aggregate_chunked(qeh_ctx *ctx, const qeh_column *keys, int n_keys, c
     return QEH_OK;
 }
 
-// Internal entry shared by qeh_hash_aggregate and the executor's fused
-// Aggregate(Filter(..)) path: `cols` = key columns then aggregate inputs.
-int hash_aggregate_filtered(qeh_ctx *ctx, const qeh_column *keys, int n_keys, const qeh_column *agg_inputs,
-                            int n_inputs, const qeh_agg *aggs, int n_aggs, const qeh_column *pred_cols,
-                            int n_pred_cols, const qeh_expr *predicate, int64_t input_batches,
-                            qeh_column *out_keys, qeh_column *out_aggs, int64_t *out_groups) {
+// The aggregate over fixed-width keys (Utf8 keys arrive as their dictionary codes).
+static int hash_aggregate_coded(qeh_ctx *ctx, const qeh_column *keys, int n_keys, const qeh_column *agg_inputs,
+                                int n_inputs, const qeh_agg *aggs, int n_aggs, const qeh_column *pred_cols,
+                                int n_pred_cols, const qeh_expr *predicate, int64_t input_batches,
+                                qeh_column *out_keys, qeh_column *out_aggs, int64_t *out_groups) {
     if (!out_groups) return fail(QEH_E_INVALID, "qeh_hash_aggregate: out_groups is NULL");
     *out_groups = 0;
     if (n_aggs == 0) return QEH_OK;  // executor.rs:163-165: no aggregates -> no batches
@@ -3848,8 +3847,7 @@ int hash_aggregate_filtered(qeh_ctx *ctx, const qeh_column *keys, int n_keys, co
         return aggregate_rows(ctx, GM_ZERO, cols, n, pp, src, specs, 1, none, nullptr, nullptr, false,
                               "aggregate_rows", out_keys, out_aggs, out_groups);
     }
-    const int kd0 = keys[0].dtype;
-    if (n_keys == 1 && kd0 != QEH_DT_UTF8 && !std::getenv("QEH_NO_LDS_GROUPBY")) {
+    if (n_keys == 1 && !std::getenv("QEH_NO_LDS_GROUPBY")) {
         // single key: one pass, LDS hash table per workgroup, HBM table for the merge
         uint64_t gcap = 1ull << 16;
         while (gcap < (uint64_t)(n / 16) && gcap < (1ull << 22)) gcap <<= 1;
@@ -3910,6 +3908,68 @@ int hash_aggregate_filtered(qeh_ctx *ctx, const qeh_column *keys, int n_keys, co
     src.gdense = gt.dense.as<uint64_t>();
     return aggregate_rows(ctx, GM_GROUP, cols, n, pp, src, specs, gt.groups, gt.keys, kd.data(),
                           gt.rep_row.as<uint32_t>(), true, "aggregate_rows", out_keys, out_aggs, out_groups);
+}
+
+// Output key columns of an aggregate over dictionary codes back to Utf8 (the NULL group keeps a
+// NULL key); on failure every output column is released.
+static int decode_utf8_group_keys(qeh_ctx *ctx, const Utf8Keys &uk, int n_keys, int n_aggs, int status, qeh_column *out_keys,
+                                  qeh_column *out_aggs, int64_t *out_groups) {
+    if (status != QEH_OK) return status;
+    for (int i = 0; i < n_keys; ++i) {
+        if (!out_keys[i].values) {  // no column was produced: only its type is the caller's
+            if (uk.dict_of_key[i] >= 0) out_keys[i].dtype = QEH_DT_UTF8;
+            continue;
+        }
+        const int s = uk.decode(i, &out_keys[i]);
+        if (s != QEH_OK) {
+            for (int j = 0; j < n_keys; ++j) qeh_column_release(ctx, &out_keys[j]);
+            for (int j = 0; j < n_aggs; ++j) qeh_column_release(ctx, &out_aggs[j]);
+            *out_groups = 0;
+            return s;
+        }
+    }
+    return QEH_OK;
+}
+
+// Internal entry shared by qeh_hash_aggregate and the executor's fused
+// Aggregate(Filter(..)) path: `cols` = key columns then aggregate inputs.  Utf8 keys are grouped
+// by their dictionary codes (built over all rows: rows the predicate drops form no groups).
+int hash_aggregate_filtered(qeh_ctx *ctx, const qeh_column *keys, int n_keys, const qeh_column *agg_inputs,
+                            int n_inputs, const qeh_agg *aggs, int n_aggs, const qeh_column *pred_cols,
+                            int n_pred_cols, const qeh_expr *predicate, int64_t input_batches,
+                            qeh_column *out_keys, qeh_column *out_aggs, int64_t *out_groups) {
+    if (!any_utf8(keys, n_keys))
+        return hash_aggregate_coded(ctx, keys, n_keys, agg_inputs, n_inputs, aggs, n_aggs, pred_cols, n_pred_cols, predicate,
+                                    input_batches, out_keys, out_aggs, out_groups);
+    if (!out_groups) return fail(QEH_E_INVALID, "qeh_hash_aggregate: out_groups is NULL");
+    *out_groups = 0;
+    if (n_aggs == 0) return QEH_OK;
+    if (n_keys > kMaxGroupKeys) return fail(QEH_E_UNSUPPORTED, "1..4 group keys supported on the device");
+    if (!out_keys || !out_aggs) return fail(QEH_E_INVALID, "qeh_hash_aggregate: output columns are NULL");
+    if (n_aggs <= kMaxAggs) {
+        // argument errors (lengths, aggregate and predicate types) before the n-row encode
+        const int64_t n = keys[0].length;
+        for (int i = 0; i < n_keys; ++i)
+            if (keys[i].length != n) return fail(QEH_E_INVALID, "aggregate columns have different lengths");
+        for (int i = 0; i < n_inputs; ++i)
+            if (agg_inputs[i].length != n) return fail(QEH_E_INVALID, "aggregate columns have different lengths");
+        for (int i = 0; i < n_pred_cols; ++i)
+            if (pred_cols[i].length != n) return fail(QEH_E_INVALID, "aggregate columns have different lengths");
+        std::vector<int> idx(std::max(n_inputs, 1), 0);
+        AggSpecs specs;
+        QEH_TRY(plan_aggs(aggs, n_aggs, agg_inputs, n_inputs, idx.data(), &specs));
+        std::vector<int32_t> dts(std::max(n_pred_cols, 1), 0);
+        for (int i = 0; i < n_pred_cols; ++i) dts[i] = pred_cols[i].dtype;
+        PredPlan pp;
+        QEH_TRY(plan_predicate(predicate, dts.data(), n_pred_cols, &pp));
+    }
+    DeviceGuard dg(ctx->device);
+    for (int i = 0; i < n_keys; ++i) out_keys[i] = qeh_column{};
+    Utf8Keys uk;
+    QEH_TRY(encode_utf8_keys(ctx, keys, n_keys, &uk));
+    const int s = hash_aggregate_coded(ctx, uk.keys.data(), n_keys, agg_inputs, n_inputs, aggs, n_aggs, pred_cols, n_pred_cols,
+                                       predicate, input_batches, out_keys, out_aggs, out_groups);
+    return decode_utf8_group_keys(ctx, uk, n_keys, n_aggs, s, out_keys, out_aggs, out_groups);
 }
 
 }  // namespace qeh
@@ -5064,6 +5124,17 @@ extern "C" int qeh_join_filter_aggregate(qeh_ctx *ctx, const qeh_column *probe_c
     QEH_TRY(plan_aggs(aggs, n_aggs, probe_cols, n_probe_cols, idx.data(), &specs));
     if (probe_cols[probe_key_idx].dtype != QEH_DT_INT64 && probe_cols[probe_key_idx].dtype != QEH_DT_INT32)
         return fail(QEH_E_UNSUPPORTED, "hash join keys must be Int32/Int64 on the device");
+    if (any_utf8(build_group_keys, n_group_keys)) {
+        // group on the build side's dictionary codes (the arguments are checked above, before the encode)
+        if (n_group_keys > kMaxGroupKeys) return fail(QEH_E_UNSUPPORTED, "1..4 group keys supported on the device");
+        if (!out_keys || !out_aggs) return fail(QEH_E_INVALID, "qeh_join_filter_aggregate: output columns are NULL");
+        for (int i = 0; i < n_group_keys; ++i) out_keys[i] = qeh_column{};
+        Utf8Keys uk;
+        QEH_TRY(encode_utf8_keys(ctx, build_group_keys, n_group_keys, &uk));
+        const int s = qeh_join_filter_aggregate(ctx, probe_cols, n_probe_cols, probe_key_idx, predicate, build_key,
+                                                uk.keys.data(), n_group_keys, aggs, n_aggs, out_keys, out_aggs, out_groups);
+        return decode_utf8_group_keys(ctx, uk, n_group_keys, n_aggs, s, out_keys, out_aggs, out_groups);
+    }
     MinMaxMemoScope memo(ctx);  // build key / group key ranges: read once for prelaunch, groups and join table
 
     // phase A of the slice path on the second queue, when its shape is known from the build key's

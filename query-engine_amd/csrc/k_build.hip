@@ -895,7 +895,8 @@ int build_group_table(qeh_ctx *ctx, const qeh_column *keys, int n_keys, int64_t 
     kc.n = n_keys;
     for (int i = 0; i < n_keys; ++i) {
         QEH_TRY(check_column(keys[i], "group key"));
-        if (keys[i].dtype == QEH_DT_UTF8) return fail(QEH_E_UNSUPPORTED, "Utf8 group keys are not supported on the device");
+        // Utf8 keys reach the table as dictionary codes (encode_utf8_keys in the aggregate entry points)
+        if (keys[i].dtype == QEH_DT_UTF8) return fail(QEH_E_INTERNAL, "Utf8 group key was not dictionary-encoded");
         if (keys[i].length != n_rows) return fail(QEH_E_INVALID, "group key length mismatch");
         kc.c[i] = make_colref(keys[i]);
     }

@@ -236,6 +236,10 @@ extern "C" int qeh_merge_sorted(qeh_ctx *ctx, const qeh_column *parts, int n_par
     }
     std::vector<qeh_column> keys(n_keys);
     for (int k = 0; k < n_keys; ++k) keys[k] = cat[key_idx[k]];
+    if (any_utf8(keys.data(), n_keys)) {  // as before qeh_sort_indices_nulls took Utf8 keys
+        release_cat();
+        return fail(QEH_E_UNSUPPORTED, "Utf8 merge keys are not supported on the device");
+    }
     qeh_column perm{};
     s = qeh_sort_indices_nulls(ctx, keys.data(), n_keys, ascending, nulls_first, &perm);
     int taken = 0;

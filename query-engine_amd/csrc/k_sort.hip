@@ -1264,7 +1264,8 @@ static int check_sort_keys(const qeh_column *keys, int n_keys, int64_t *n) {
     *n = keys[0].length;
     for (int j = 0; j < n_keys; ++j) {
         QEH_TRY(check_column(keys[j], "sort key"));
-        if (keys[j].dtype == QEH_DT_UTF8) return fail(QEH_E_UNSUPPORTED, "Utf8 sort keys are not supported on the device");
+        // Utf8 keys reach the sort as dictionary codes (encode_utf8_keys at the entry points)
+        if (keys[j].dtype == QEH_DT_UTF8) return fail(QEH_E_INTERNAL, "Utf8 sort key was not dictionary-encoded");
         if (keys[j].length != *n) return fail(QEH_E_INVALID, "sort keys have different lengths");
     }
     return QEH_OK;
@@ -1642,6 +1643,11 @@ extern "C" int qeh_sort_indices(qeh_ctx *ctx, const qeh_column *keys, int n_keys
                                 qeh_column *out_perm) {
     if (!ctx || !keys || !out_perm) return fail(QEH_E_INVALID, "qeh_sort_indices: bad argument");
     DeviceGuard dg(ctx->device);
+    if (any_utf8(keys, n_keys)) {  // codes compare as the strings do
+        Utf8Keys uk;
+        QEH_TRY(encode_utf8_keys(ctx, keys, n_keys, &uk));
+        return qeh_sort_indices(ctx, uk.keys.data(), n_keys, ascending, out_perm);
+    }
     int64_t n;
     QEH_TRY(check_sort_keys(keys, n_keys, &n));
     RadixState rs;
@@ -2274,6 +2280,11 @@ extern "C" int qeh_sort_indices_nulls(qeh_ctx *ctx, const qeh_column *keys, int 
                                       const int8_t *nulls_first, qeh_column *out_perm) {
     if (!ctx || !keys || !out_perm) return fail(QEH_E_INVALID, "qeh_sort_indices_nulls: bad argument");
     DeviceGuard dg(ctx->device);
+    if (any_utf8(keys, n_keys)) {
+        Utf8Keys uk;
+        QEH_TRY(encode_utf8_keys(ctx, keys, n_keys, &uk));
+        return qeh_sort_indices_nulls(ctx, uk.keys.data(), n_keys, ascending, nulls_first, out_perm);
+    }
     int64_t n;
     QEH_TRY(check_sort_keys(keys, n_keys, &n));
     RadixState rs;
@@ -2317,6 +2328,12 @@ extern "C" int qeh_row_number(qeh_ctx *ctx, const qeh_column *part_keys, int n_p
     if (!ctx || !out_rn || (n_part + n_order) < 1) return fail(QEH_E_INVALID, "qeh_row_number: bad argument");
     if (n_part > kMaxGroupKeys) return fail(QEH_E_UNSUPPORTED, "at most 4 PARTITION BY keys on the device");
     DeviceGuard dg(ctx->device);
+    if (any_utf8(part_keys, n_part) || any_utf8(order_keys, n_order)) {
+        Utf8Keys pk, ok;
+        QEH_TRY(encode_utf8_keys(ctx, part_keys, n_part, &pk));
+        QEH_TRY(encode_utf8_keys(ctx, order_keys, n_order, &ok));
+        return qeh_row_number(ctx, pk.keys.data(), n_part, ok.keys.data(), n_order, ascending, out_rn);
+    }
     std::vector<qeh_column> all;
     std::vector<int8_t> asc;
     for (int j = 0; j < n_part; ++j) {
@@ -2551,6 +2568,12 @@ extern "C" int qeh_window(qeh_ctx *ctx, int32_t func, const qeh_column *part_key
             return fail(QEH_E_UNSUPPORTED, "window value functions take Int32/Int64/Float32/Float64 on the device");
     }
     DeviceGuard dg(ctx->device);
+    if (any_utf8(part_keys, n_part) || any_utf8(order_keys, n_order)) {  // Utf8 `arg` stays unsupported (above)
+        Utf8Keys pk, ok;
+        QEH_TRY(encode_utf8_keys(ctx, part_keys, n_part, &pk));
+        QEH_TRY(encode_utf8_keys(ctx, order_keys, n_order, &ok));
+        return qeh_window(ctx, func, pk.keys.data(), n_part, ok.keys.data(), n_order, ascending, arg, param, dflt, out);
+    }
     std::vector<qeh_column> all;
     std::vector<int8_t> asc;
     for (int j = 0; j < n_part; ++j) all.push_back(part_keys[j]), asc.push_back(1);

@@ -149,6 +149,29 @@ struct Utf8Rewrite {
 int rewrite_utf8_compares(qeh_ctx *ctx, const qeh_column *cols, int n_cols, const qeh_expr *e, Utf8Rewrite *out);
 bool expr_has_utf8(const qeh_expr *e, const int32_t *dtypes, int n_cols);
 
+// Utf8 key columns (k_utf8_dict.hip): every QEH_DT_UTF8 column of `keys` is replaced in `keys` by
+// its INT32 order-preserving dictionary codes (each Utf8 column gets its own dictionary), so the
+// integer sort / group / window paths take it.  Owns the code and dictionary columns.  decode()
+// turns an operator's output code column for key `key` back into a Utf8 column (NULL stays NULL);
+// a key that was not Utf8 is left alone.
+struct Utf8Keys {
+    qeh_ctx *ctx = nullptr;
+    std::vector<qeh_column> keys;
+    std::vector<qeh_column> codes, dicts;
+    std::vector<int> dict_of_key;
+    Utf8Keys() = default;
+    Utf8Keys(const Utf8Keys &) = delete;
+    Utf8Keys &operator=(const Utf8Keys &) = delete;
+    ~Utf8Keys();
+    int decode(int key, qeh_column *col) const;
+};
+int encode_utf8_keys(qeh_ctx *ctx, const qeh_column *keys, int n_keys, Utf8Keys *out);
+inline bool any_utf8(const qeh_column *cols, int n) {
+    for (int i = 0; cols && i < n; ++i)
+        if (cols[i].dtype == QEH_DT_UTF8) return true;
+    return false;
+}
+
 // Window functions over one bounded integer PARTITION BY key and one ORDER BY key by partitioning
 // (k_window.hip): ROW_NUMBER / RANK / DENSE_RANK / NTILE into a fresh Int64 column.
 // kWindowMsdNotEligible (nothing allocated) when the shapes do not fit.

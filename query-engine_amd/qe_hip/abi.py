@@ -109,6 +109,7 @@ SIGNATURES = {
     "qeh_shuffle_items_finish": (I, [P, P, P, P, P, C.POINTER(I64), P, U64, P, I, I64, P]),
     "qeh_fused_items_check": (I, [P, COLP, I, I, EXPRP, AGGP, I]),
     "qeh_join_filter_aggregate_prelaunch_stats": (I, [P, COLP, I, I, EXPRP, AGGP, I, P, I, I]),
+    "qeh_utf8_dict_encode": (I, [P, COLP, COLP, COLP]),
     "qeh_sort_indices": (I, [P, COLP, I, C.POINTER(C.c_int8), COLP]),
     "qeh_sort_indices_nulls": (I, [P, COLP, I, C.POINTER(C.c_int8), C.POINTER(C.c_int8), COLP]),
     "qeh_concat": (I, [P, COLP, I, COLP]),

@@ -616,6 +616,13 @@ class Context:
                                                                C.byref(e) if e is not None else None, ca, len(aggs),
                                                                br, gr))
 
+    def utf8_dict_encode(self, col: DeviceColumn) -> Tuple[DeviceColumn, DeviceColumn]:
+        """qeh_utf8_dict_encode: (Int32 codes with the column's validity, Utf8 dictionary of the
+        distinct non-NULL strings in ascending byte order); codes compare as the strings do."""
+        codes, dic = abi.QehColumn(), abi.QehColumn()
+        abi.check(self.lib.qeh_utf8_dict_encode(self.h, C.byref(col.c), C.byref(codes), C.byref(dic)))
+        return self._wrap(codes), self._wrap(dic)
+
     def sort_indices(self, keys: Sequence[DeviceColumn], ascending: Sequence[bool]) -> DeviceColumn:
         ck = self._cols(keys)
         asc = (C.c_int8 * max(len(keys), 1))(*[1 if a else 0 for a in ascending])

@@ -166,6 +166,13 @@ def _all_to_all(p: torch.Tensor, pin: Sequence[int], pout: Sequence[int], peak: 
     return out
 
 
+def _refuse_utf8_keys(keys: Sequence[DeviceColumn], what: str) -> None:
+    """Utf8 keys are a single-device feature: a distributed operator would need one dictionary
+    shared by the ranks' columns."""
+    if any(k.dtype == abi.DT_UTF8 for k in keys):
+        raise abi.QehError(abi.QEH_E_UNSUPPORTED, f"Utf8 {what} keys are not supported in the distributed layer")
+
+
 def _without_bitmap(ctx: Context, col: DeviceColumn) -> DeviceColumn:
     """A view of `col` without its validity bitmap (for columns known to hold no NULL)."""
     c = abi.QehColumn()
@@ -451,6 +458,7 @@ class DistributedExecutor:
         for f, _ in aggs:
             if f not in FINAL_OF:
                 raise NotImplementedError("distributed AVG needs SUM+COUNT partials; compose it from them")
+        _refuse_utf8_keys(keys, "group")
         pk, pa_, g = self.ctx.hash_aggregate(keys, inputs, aggs)
         if g == 0:
             pk, pa_ = self._empty_partials(keys, inputs, aggs)
@@ -1201,6 +1209,7 @@ class DistributedExecutor:
         all-to-all into this rank's input order (_moved_window, or a permutation and
         a scatter for shapes it does not take)."""
         cols = list(part_keys) + list(order_keys)
+        _refuse_utf8_keys(cols, "window")
         if self._moved_shuffle_ok(part_keys, cols):
             npk = len(part_keys)
             return self._moved_window(part_keys, cols,
@@ -1222,6 +1231,7 @@ class DistributedExecutor:
         through the inverse permutation (the results of LAG/LEAD/… carry NULLs)."""
         if not part_keys:
             raise ValueError("distributed window functions need a PARTITION BY key")
+        _refuse_utf8_keys(list(part_keys) + list(order_keys), "window")
         cols = list(part_keys) + list(order_keys) + ([arg] if arg is not None else [])
         npk, nok = len(part_keys), len(order_keys)
         if func in (W.RowNumber, W.Rank, W.DenseRank, W.Ntile) and self._moved_shuffle_ok(part_keys, cols):

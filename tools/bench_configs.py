@@ -16,12 +16,16 @@
   partition  device side of a hash Exchange, 1e8 rows into 8 partitions
   cfg5leg    config 5's per-rank device leg at N = 8 (8-way exchange pass, local ROW_NUMBER over the
              received rows, the unmove pass that returns the numbers to input order)
+  utf8_groupby  GROUP BY a Utf8 key: 1e8 rows over 1024 distinct strings of 8-24 bytes, COUNT + SUM of an
+             Int64 column; beside it the same query over the pre-encoded Int32 codes and the
+             dictionary encode alone against its floor (offsets + string bytes read, codes written)
+  utf8_sort  ORDER BY a Utf8 key: 1e8 rows of all-distinct 16-byte strings; same companions
   cfg4leg    config 4's per-rank device leg at N = 8 (fused filter + 8-way exchange pass over 1e9
              rows, the dim shard's exchange pass, the local join of what the rank receives)
 
 Prints one JSON line per config: rows/s, ms per run, algorithmic GB/s and
 fraction of 8 TB/s, and the oracle's rows/s on a bounded sample (1 thread).
-usage: python tools/bench_configs.py [--only cfg2,cfg3,cfg5,window,filter,limit,plan,left,full,merge,encode,partition] [--scale 1.0]
+usage: python tools/bench_configs.py [--only cfg2,cfg3,cfg5,window,filter,limit,plan,left,full,merge,encode,partition,utf8_groupby,utf8_sort] [--scale 1.0]
 """
 import argparse
 import json
@@ -698,6 +702,78 @@ def cfg_plan(ctx, scale):
         qx.cache_evict()
 
 
+UTF8_DICT_KERNELS = ["utf8_dict_insert", "utf8_dict_compact", "utf8_dict_order", "utf8_dict_codes", "radix_pass",
+                     "sort_encode", "scan"]
+
+
+def upload_utf8_raw(ctx, offs, data):
+    """A non-null Utf8 device column from host int32 offsets and uint8 bytes (no Python strings)."""
+    from qe_hip.device import DeviceColumn
+    po, pd = ctx.alloc(offs.nbytes), ctx.alloc(max(data.nbytes, 8))
+    ctx.h2d(po, offs)
+    ctx.h2d(pd, data)
+    c = abi.QehColumn(dtype=abi.DT_UTF8, owned=0, length=len(offs) - 1, offset=0, null_count=0, values=pd, offsets=po,
+                      values_bytes=int(offs[-1]))
+    return DeviceColumn(ctx, c, [po, pd])
+
+
+def utf8_key_report(ctx, cfg, n, key, string_bytes, op_utf8, op_codes, op_kernels, reps=5):
+    """One line: the query over the Utf8 key, the same query over its pre-encoded Int32 codes (the
+    existing integer path, same process), the encode step alone and its share, and the encode
+    pass against its floor (offsets read + string bytes read + codes written, at 8 TB/s)."""
+    def enc():
+        c, d = ctx.utf8_dict_encode(key)
+        c.release()
+        d.release()
+    enc_wall, enc_kt, _ = timed(ctx, enc, reps, UTF8_DICT_KERNELS)
+    codes, dic = ctx.utf8_dict_encode(key)
+    wall_u, kt_u, _ = timed(ctx, lambda: op_utf8(key), reps, list(dict.fromkeys(UTF8_DICT_KERNELS + op_kernels)))
+    wall_c, kt_c, _ = timed(ctx, lambda: op_codes(codes), reps, op_kernels)
+    alg = 4.0 * (n + 1) + string_bytes + 4.0 * n
+    floor_ms = alg / (PEAK * 1e9) * 1e3
+    enc_kernel_ms = sum(enc_kt.values())
+    line(cfg, n, wall_u, alg, enc_kernel_ms, "k_dict_insert (+ compact, order, codes)", None,
+         {"distinct": len(dic), "utf8_key_wall_ms": wall_u * 1e3, "utf8_key_kernel_ms": sum(kt_u.values()),
+          "int32_codes_wall_ms": wall_c * 1e3, "int32_codes_kernel_ms": sum(kt_c.values()),
+          "encode_wall_ms": enc_wall * 1e3, "encode_kernel_ms": enc_kernel_ms,
+          "encode_kernels_ms": enc_kt, "encode_share_of_wall": enc_wall / wall_u,
+          "encode_floor_ms": floor_ms, "encode_frac_of_floor": floor_ms / enc_kernel_ms if enc_kernel_ms else None,
+          "encode_wall_frac_of_floor": floor_ms / (enc_wall * 1e3)})
+
+
+def cfg_utf8_groupby(ctx, scale):
+    """SELECT s, COUNT(v), SUM(v) FROM t GROUP BY s: 1e8 rows over 1024 distinct strings of 8-24 bytes."""
+    n, nd = int(1e8 * scale), 1024
+    r = np.random.default_rng(SEED)
+    pool = [bytes(r.integers(97, 123, int(l), dtype=np.uint8)) + b"%04d" % i for i, l in enumerate(r.integers(4, 21, nd))]
+    small = ctx.upload(pool)
+    k = ctx.generate(abi.GEN_UNIFORM_MOD, SEED, 2, n, nd)
+    key = ctx.take(small, k)  # the 1e8-row Utf8 column, gathered on the device
+    v = ctx.generate(abi.GEN_UNIFORM_MOD, SEED, 4, n, 2 ** 21, lo=-(2 ** 20))
+    aggs = [(AF.Count, 0), (AF.Sum, 0)]
+    utf8_key_report(ctx, "utf8 group-by 1e8 rows, 1024 strings of 8-24 B", n, key, float(key.c.values_bytes),
+                    lambda kc: ctx.hash_aggregate([kc], [v], aggs), lambda kc: ctx.hash_aggregate([kc], [v], aggs),
+                    ["aggregate_rows", "group_insert", "gather"])
+
+
+def cfg_utf8_sort(ctx, scale):
+    """SELECT ... ORDER BY s: 1e8 rows of all-distinct 16-byte strings."""
+    n = int(1e8 * scale)
+    hexd = np.frombuffer(b"0123456789abcdef", np.uint8)
+    data = np.empty(n * 16, np.uint8)
+    shifts = np.arange(60, -4, -4, dtype=np.uint64)
+    step = 5_000_000
+    for a in range(0, n, step):  # 16 hex digits of a bijection of the row number
+        x = np.arange(a, min(a + step, n), dtype=np.uint64) * np.uint64(0x9E3779B97F4A7C15) + np.uint64(SEED)
+        data[a * 16:(a + len(x)) * 16] = hexd[((x[:, None] >> shifts) & np.uint64(15)).astype(np.intp)].ravel()
+    offs = (np.arange(n + 1, dtype=np.int64) * 16).astype(np.int32)
+    key = upload_utf8_raw(ctx, offs, data)
+    del data
+    utf8_key_report(ctx, "utf8 order-by 1e8 rows, all-distinct 16 B strings", n, key, 16.0 * n,
+                    lambda kc: ctx.sort_indices([kc], [True]), lambda kc: ctx.sort_indices([kc], [True]),
+                    ["radix_pass", "sort_encode"], reps=3)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--only", default="cfg2,cfg3,cfg5,filter")
@@ -713,7 +789,7 @@ def main():
          "plan": cfg_plan, "left": lambda c, s: cfg_outer(c, s, 1), "full": lambda c, s: cfg_outer(c, s, 3),
          "merge": cfg_merge, "encode": cfg_encode, "shapes": cfg_metric_shapes, "partition": cfg_partition, "cfg3w": cfg3_wide, "window": cfg_window,
          "cfg4leg": cfg4_leg, "cfg4items": cfg4_items_leg, "cfg5leg": cfg5_leg,
-         "window_lsd": cfg_window_lsd}[name](ctx, args.scale)
+         "window_lsd": cfg_window_lsd, "utf8_groupby": cfg_utf8_groupby, "utf8_sort": cfg_utf8_sort}[name](ctx, args.scale)
         ctx.sync()
         abi.check(ctx.lib.qeh_pool_trim(ctx.h))
     ctx.close()
