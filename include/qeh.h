@@ -230,7 +230,8 @@ int qeh_filter_aggregate(qeh_ctx *ctx, const qeh_column *cols, int n_cols, const
  * reference ignores `on`).  Builds a hash table on
  * `build_key`, probes with `probe_key` (NULL keys never match), and emits the
  * matching (probe row, build row) pairs with probe payload columns first
- * (left ++ right, executor.rs:532-537).  Row order unspecified.              */
+ * (left ++ right, executor.rs:532-537).  Row order unspecified.  Keys are
+ * Int32 / Int64 (else QEH_E_UNSUPPORTED); Utf8 keys go through qeh_hash_join. */
 int qeh_hash_join_inner(qeh_ctx *ctx, const qeh_column *probe_key, const qeh_column *probe_cols,
                         int n_probe_cols, const qeh_column *build_key,
                         const qeh_column *build_cols, int n_build_cols, qeh_column *out_probe,
@@ -245,10 +246,22 @@ int qeh_hash_join_inner(qeh_ctx *ctx, const qeh_column *probe_key, const qeh_col
  * Row order: preserved side's row order, FULL's unmatched right rows last (compare as multisets).
  * LEFT / RIGHT over a unique Int-keyed build side whose payloads are non-null 8-byte columns
  * return the preserved side's columns as views of the inputs (owned = 0, like arrow's column
- * clones): keep the inputs alive while using them; every other output is owned. */
+ * clones): keep the inputs alive while using them; every other output is owned.
+ * Utf8 keys are QEH_E_UNSUPPORTED here; qeh_hash_join takes them. */
 int qeh_hash_join_outer(qeh_ctx *ctx, int join_type, const qeh_column *left_key, const qeh_column *left_cols,
                         int n_left_cols, const qeh_column *right_key, const qeh_column *right_cols, int n_right_cols,
                         qeh_column *out_left, qeh_column *out_right, int64_t *out_rows);
+
+/* Equi-join on one key of any supported type: the contract of qeh_hash_join_outer (join_type
+ * 0 INNER, 1 LEFT, 2 RIGHT, 3 FULL; its row order and owned / view rules).  Int32 / Int64 keys are
+ * forwarded unchanged.  Two Utf8 keys are replaced by their shared dictionary codes
+ * (qeh_utf8_join_encode, the dictionary built over the side the join builds its table on) and the
+ * integer join runs on the codes; the payload columns are the caller's, so a Utf8 key listed among
+ * them comes back as Utf8.  One Utf8 key against a non-Utf8 one is QEH_E_TYPE with arrow's
+ * message ("Invalid argument error: Invalid comparison operation: Utf8 == Int64"). */
+int qeh_hash_join(qeh_ctx *ctx, int join_type, const qeh_column *left_key, const qeh_column *left_cols, int n_left_cols,
+                  const qeh_column *right_key, const qeh_column *right_cols, int n_right_cols,
+                  qeh_column *out_left, qeh_column *out_right, int64_t *out_rows);
 
 /* Fused filter -> hash-join -> group-by (the BASELINE metric path):
  *   SELECT <build group keys>, AGG(probe cols)... FROM probe JOIN build
@@ -446,6 +459,22 @@ int qeh_fused_items_check(qeh_ctx *ctx, const qeh_column *probe_cols, int n_prob
  * D > INT32_MAX -> QEH_E_UNSUPPORTED.  The sort, aggregate and window entry points below use
  * it for their Utf8 key columns (one dictionary per column). */
 int qeh_utf8_dict_encode(qeh_ctx *ctx, const qeh_column *col, qeh_column *out_codes, qeh_column *out_dict);
+
+/* Equality codes of two Utf8 columns from one dictionary, for equi-join keys.  The dictionary is
+ * built over `build`; `probe` is looked up in it.  Both must be Utf8 (else QEH_E_INVALID), at most
+ * 2^32-2 rows each; either may be empty, carry a validity bitmap or a non-zero offset.
+ * out_build_codes: INT32, validity = the build column's (none if it has none).  Two valid build
+ *   rows have equal codes exactly when their bytes are equal; every code lies in [0, D), D = the
+ *   number of distinct non-NULL build strings (*out_distinct; the pointer may be NULL).
+ *   The codes are NOT ordered: which string gets which code is unspecified (equality only --
+ *   use qeh_utf8_dict_encode where the order of the codes matters).
+ * out_probe_codes: INT32 with a validity bitmap (null_count -1).  A probe row is valid exactly
+ *   when it is non-NULL and its bytes occur among the non-NULL build rows, and then carries that
+ *   build string's code; every other row holds 0 with its bit cleared (a NULL key never matches
+ *   in a join, so "absent from the build side" and "NULL" are the same to it).
+ * The empty string is a value, not NULL; strings compare as bytes, as k_utf8_cmp does. */
+int qeh_utf8_join_encode(qeh_ctx *ctx, const qeh_column *build, const qeh_column *probe,
+                         qeh_column *out_build_codes, qeh_column *out_probe_codes, int64_t *out_distinct);
 
 /* Stable lexicographic sort -> permutation (UINT32 row ids) of the input.
  * Intended semantics of `Sort` (physical_plan.rs:40-44; executor.rs:290-297

@@ -734,13 +734,22 @@ class Executor {
             rows = m;
         } else {
             int lk, rk;
-            if (!equi_keys(nd.predicate, (int)l.cols.size(), &lk, &rk) || !int_key(lc[lk]) || !int_key(rc[rk]))
+            if (!equi_keys(nd.predicate, (int)l.cols.size(), &lk, &rk) || !key_pair(lc[lk], rc[rk]))
                 return join_general(nd, l, r, out);
+            qeh_column lkey = lc[lk], rkey = rc[rk];
+            Col lcodes, rcodes;
+            if (lkey.dtype == QEH_DT_UTF8) {
+                // the codes of one dictionary, built over the side the join builds its table on
+                if (nd.join_type == QEH_JOIN_RIGHT) QEH_TRY(join_codes(lkey, rkey, &lcodes, &rcodes));
+                else QEH_TRY(join_codes(rkey, lkey, &rcodes, &lcodes));
+                lkey = lcodes.c;
+                rkey = rcodes.c;
+            }
             if (nd.join_type == QEH_JOIN_INNER)
-                QEH_TRY(qeh_hash_join_inner(ctx_, &lc[lk], lc.data(), (int)lc.size(), &rc[rk], rc.data(), (int)rc.size(),
+                QEH_TRY(qeh_hash_join_inner(ctx_, &lkey, lc.data(), (int)lc.size(), &rkey, rc.data(), (int)rc.size(),
                                             lo.data(), ro.data(), &rows));
             else  // LEFT / RIGHT / FULL
-                QEH_TRY(qeh_hash_join_outer(ctx_, nd.join_type, &lc[lk], lc.data(), (int)lc.size(), &rc[rk], rc.data(),
+                QEH_TRY(qeh_hash_join_outer(ctx_, nd.join_type, &lkey, lc.data(), (int)lc.size(), &rkey, rc.data(),
                                             (int)rc.size(), lo.data(), ro.data(), &rows));
             // a column returned as a view (owned = 0: an outer join's preserved side) keeps the
             // input's owner alive
@@ -753,6 +762,20 @@ class Executor {
     }
 
     static bool int_key(const qeh_column &c) { return c.dtype == QEH_DT_INT64 || c.dtype == QEH_DT_INT32; }
+    // two columns a hash join can key on: both integer, or both Utf8 (joined on their shared codes)
+    static bool key_pair(const qeh_column &a, const qeh_column &b) {
+        return (int_key(a) && int_key(b)) || (a.dtype == QEH_DT_UTF8 && b.dtype == QEH_DT_UTF8);
+    }
+
+    // The INT32 codes of two Utf8 join key columns from one dictionary built over `build`
+    // (qeh_utf8_join_encode): equal codes <=> equal strings, absent and NULL probe rows are NULL.
+    int join_codes(const qeh_column &build, const qeh_column &probe, Col *build_codes, Col *probe_codes) {
+        qeh_column b{}, p{};
+        QEH_TRY(utf8_join_encode(ctx_, build, probe, &b, &p, nullptr));
+        *build_codes = own(ctx_, b);
+        *probe_codes = own(ctx_, p);
+        return QEH_OK;
+    }
 
     // Postfix ranges [b, e) of the AND-ed conjuncts of `e` (nested ANDs flattened).  A malformed
     // expression yields itself as the only conjunct (its evaluation reports the error).
@@ -793,7 +816,8 @@ class Executor {
         *out = found;
     }
 
-    // One conjunct `Column(a) = Column(b)` with one side in each input and integer keys.
+    // One conjunct `Column(a) = Column(b)` with one side in each input and integer keys, or Utf8 on
+    // both sides (a key through the two columns' shared dictionary codes).
     static bool equi_conjunct(const qeh_expr_node *x, int len, int nl, const std::vector<qeh_column> &lc,
                               const std::vector<qeh_column> &rc, int *lk, int *rk) {
         if (len != 3 || x[0].kind != QEH_EX_COLUMN || x[1].kind != QEH_EX_COLUMN || x[2].kind != QEH_EX_BINARY ||
@@ -802,21 +826,21 @@ class Executor {
         int a = x[0].index, b = x[1].index;
         if (a >= nl && b < nl) std::swap(a, b);
         if (!(a >= 0 && a < nl && b >= nl && b - nl < (int)rc.size())) return false;
-        if (!int_key(lc[a]) || !int_key(rc[b - nl])) return false;
+        if (!key_pair(lc[a], rc[b - nl])) return false;
         *lk = a;
         *rk = b - nl;
         return true;
     }
 
     // Pack several key columns of each side into one Int64 key column per side (k_pack_keys).
-    int pack_keys(const std::vector<qeh_column> &lc, const std::vector<int> &lk, const std::vector<qeh_column> &rc,
-                  const std::vector<int> &rk, Col *lkey, Col *rkey, bool *hashed) {
+    // `lk[j]` / `rk[j]`: the j-th key column of each side (integer; Utf8 keys arrive as their codes).
+    int pack_keys(const std::vector<qeh_column> &lk, const std::vector<qeh_column> &rk, Col *lkey, Col *rkey, bool *hashed) {
         const int nk = (int)lk.size();
         PackSpec ps{};
         ps.n = nk;
         int bits = 0;
         for (int j = 0; j < nk; ++j) {
-            const qeh_column pair[2] = {lc[lk[j]], rc[rk[j]]};
+            const qeh_column pair[2] = {lk[j], rk[j]};
             int64_t mn[2], mx[2], cnt[2];
             QEH_TRY(columns_minmax(ctx_, pair, 2, mn, mx, cnt));
             int64_t lo = INT64_MAX, hi = INT64_MIN;
@@ -833,12 +857,11 @@ class Executor {
         ps.hash = bits > 63 ? 1 : 0;
         *hashed = ps.hash != 0;
         for (int side = 0; side < 2; ++side) {
-            const auto &cols = side == 0 ? lc : rc;
             const auto &ks = side == 0 ? lk : rk;
             KeyCols kc{};
             kc.n = nk;
             int64_t n = 0;
-            for (int j = 0; j < nk; ++j) kc.c[j] = make_colref(cols[ks[j]]), n = cols[ks[j]].length;
+            for (int j = 0; j < nk; ++j) kc.c[j] = make_colref(ks[j]), n = ks[j].length;
             qeh_column c{};
             QEH_TRY(alloc_column(ctx_, QEH_DT_INT64, n, true, &c));
             Col held = own(ctx_, c);
@@ -892,8 +915,9 @@ class Executor {
         return QEH_OK;
     }
 
-    // Join whose `on` is not a single integer equi-key: AND-ed equi conjuncts become the hash key
-    // (packed when there are several), everything else is checked by evaluating the whole `on`
+    // Join whose `on` is not a single equi-key: AND-ed equi conjuncts (integer columns, or Utf8
+    // columns through their shared dictionary codes) become the hash key (packed when there are
+    // several), everything else is checked by evaluating the whole `on`
     // over the candidate pairs; with no equi conjunct the candidates are the Cartesian product
     // (left row-major, as join_batches builds it).  LEFT / RIGHT / FULL add the rows no
     // surviving pair references, the other side NULL.  Output row order: the matching pairs,
@@ -934,13 +958,27 @@ class Executor {
             QEH_HIP(hipGetLastError());
             need_check = true;
         } else {
+            // key columns; a Utf8 pair is keyed by its shared codes (the right side builds the table)
+            std::vector<qeh_column> lkc, rkc;
+            std::vector<Col> codes;
+            for (size_t j = 0; j < lks.size(); ++j) {
+                lkc.push_back(lc[lks[j]]);
+                rkc.push_back(rc[rks[j]]);
+                if (lkc[j].dtype != QEH_DT_UTF8) continue;
+                Col bc, pc;
+                QEH_TRY(join_codes(rkc[j], lkc[j], &bc, &pc));
+                lkc[j] = pc.c;
+                rkc[j] = bc.c;
+                codes.push_back(bc);
+                codes.push_back(pc);
+            }
             Col lkey, rkey;
             if (lks.size() == 1) {
-                lkey.c = lc[lks[0]];
-                rkey.c = rc[rks[0]];
+                lkey.c = lkc[0];
+                rkey.c = rkc[0];
             } else {
                 bool hashed = false;
-                QEH_TRY(pack_keys(lc, lks, rc, rks, &lkey, &rkey, &hashed));
+                QEH_TRY(pack_keys(lkc, rkc, &lkey, &rkey, &hashed));
                 need_check = need_check || hashed;
             }
             Col lid, rid;
@@ -1085,7 +1123,9 @@ class Executor {
             int lk, rk;
             const bool keys_ok = equi_keys(jn->predicate, nl, &lk, &rk);
             const bool pred_left = !pred || (expr_columns(pred) >> nl) == 0;
-            if (keys_ok && pred_left && all_columns(nd.exprs, nd.n_exprs, nl, nl + nr) &&
+            // a Utf8 key adds its code column to the probe columns of the one kernel
+            const bool room = !(keys_ok && l.cols[lk].c.dtype == QEH_DT_UTF8) || nl < kMaxCols;
+            if (keys_ok && room && pred_left && all_columns(nd.exprs, nd.n_exprs, nl, nl + nr) &&
                 all_columns(aexprs.data(), nd.n_aggs, 0, nl) && l.batches > 0 && r.batches > 0) {
                 auto lc = raw(l), rc = raw(r);
                 std::vector<qeh_column> gk;
@@ -1094,7 +1134,18 @@ class Executor {
                 for (int i = 0; i < nd.n_aggs; ++i) qa[i] = {aggs[i].func, expr_as_column(&aexprs[i])};
                 std::vector<qeh_column> ok(gk.size()), oa(qa.size());
                 int64_t g = 0;
-                QEH_TRY(qeh_join_filter_aggregate(ctx_, lc.data(), nl, lk, pred, &rc[rk], gk.data(), (int)gk.size(),
+                // Utf8 keys: the probe codes are appended to the probe columns (the predicate and
+                // the aggregates may read the Utf8 column itself), the build codes are the build key
+                qeh_column bkey = rc[rk];
+                int pk = lk;
+                Col bcodes, pcodes;
+                if (lc[lk].dtype == QEH_DT_UTF8 && bkey.dtype == QEH_DT_UTF8) {
+                    QEH_TRY(join_codes(bkey, lc[lk], &bcodes, &pcodes));
+                    bkey = bcodes.c;
+                    pk = (int)lc.size();
+                    lc.push_back(pcodes.c);
+                }
+                QEH_TRY(qeh_join_filter_aggregate(ctx_, lc.data(), (int)lc.size(), pk, pred, &bkey, gk.data(), (int)gk.size(),
                                                   qa.data(), (int)qa.size(), ok.data(), oa.data(), &g));
                 for (int i = 0; i < nd.n_exprs; ++i) {
                     const Field &f = r.fields[expr_as_column(&nd.exprs[i]) - nl];

@@ -1224,3 +1224,32 @@ extern "C" int qeh_hash_join_outer(qeh_ctx *ctx, int join_type, const qeh_column
     *out_rows = m;
     return QEH_OK;
 }
+
+// One entry point for any key type (include/qeh.h): integer keys are forwarded; two Utf8 keys join on
+// their shared dictionary codes (qeh_utf8_join_encode), the dictionary built over the side the join
+// builds its table on (the right side, the left one for RIGHT).  The payload columns are the caller's,
+// so a Utf8 key passed as a payload comes back as Utf8.
+extern "C" int qeh_hash_join(qeh_ctx *ctx, int join_type, const qeh_column *left_key, const qeh_column *left_cols,
+                             int n_left_cols, const qeh_column *right_key, const qeh_column *right_cols, int n_right_cols,
+                             qeh_column *out_left, qeh_column *out_right, int64_t *out_rows) {
+    if (!ctx || !left_key || !right_key || !out_rows) return fail(QEH_E_INVALID, "qeh_hash_join: bad argument");
+    *out_rows = 0;
+    const bool lu = left_key->dtype == QEH_DT_UTF8, ru = right_key->dtype == QEH_DT_UTF8;
+    if (lu != ru)
+        return fail(QEH_E_TYPE, std::string("Invalid argument error: Invalid comparison operation: ") +
+                                    arrow_type_name(left_key->dtype) + " == " + arrow_type_name(right_key->dtype));
+    if (!lu)
+        return qeh_hash_join_outer(ctx, join_type, left_key, left_cols, n_left_cols, right_key, right_cols, n_right_cols,
+                                   out_left, out_right, out_rows);
+    if (join_type < 0 || join_type > 3) return fail(QEH_E_INVALID, "join type must be INNER (0), LEFT (1), RIGHT (2) or FULL (3)");
+    DeviceGuard dg(ctx->device);
+    const bool build_left = join_type == 2;
+    qeh_column bcodes{}, pcodes{};
+    QEH_TRY(utf8_join_encode(ctx, build_left ? *left_key : *right_key, build_left ? *right_key : *left_key, &bcodes, &pcodes,
+                             nullptr));
+    const int s = qeh_hash_join_outer(ctx, join_type, build_left ? &bcodes : &pcodes, left_cols, n_left_cols,
+                                      build_left ? &pcodes : &bcodes, right_cols, n_right_cols, out_left, out_right, out_rows);
+    qeh_column_release(ctx, &bcodes);
+    qeh_column_release(ctx, &pcodes);
+    return s;
+}

@@ -86,7 +86,7 @@ static const char *op_text(int op) {  // arrow-rs cmp Op display
     }
 }
 
-static const char *arrow_type_name(int dt) {
+const char *arrow_type_name(int dt) {
     switch (dt) {
         case QEH_DT_NULL: return "Null";
         case QEH_DT_BOOL: return "Boolean";

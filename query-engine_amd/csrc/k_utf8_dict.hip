@@ -21,6 +21,11 @@
 //  (d) rank[slot], then codes[i] = rank[slot_of_row[i]] in one streaming pass; the dictionary is
 //      gather_column over the sorted representatives.
 //
+// Join keys (qeh_utf8_join_encode) need equality only and one dictionary for two columns: (a) and
+// the occupancy scan of (b) run over the build column, whose codes are dense[slot_of_row[i]] -- dense
+// in [0, D) but unordered, (c) is skipped -- and k_dict_lookup streams the probe column once against
+// the finished table: a probe string found there takes the build string's code, any other row is NULL.
+//
 // All traffic between workgroups inside one launch goes through atomic words of the table and the
 // control words; the only bytes a lane compares against are the input column's, which no launch
 // writes.  Every kernel loop is bounded; no lane waits on another.
@@ -230,7 +235,9 @@ __global__ void k_dict_slot_ranks(const uint64_t *__restrict__ table, uint64_t c
         rank_of_slot[s] = table[s] != 0 ? rank_of_rep[dense[s]] : 0u;
 }
 
-__global__ void k_dict_codes(ColRef valid, const uint32_t *__restrict__ slot_of_row, const uint32_t *__restrict__ rank_of_slot,
+// (R = uint32_t: the ranks of (c); R = uint64_t: the scan's dense ids, the unordered join codes)
+template <typename R>
+__global__ void k_dict_codes(ColRef valid, const uint32_t *__restrict__ slot_of_row, const R *__restrict__ rank_of_slot,
                              int64_t n, int32_t *__restrict__ codes, uint64_t *__restrict__ out_valid) {
     const int lane = threadIdx.x & 63;
     const int64_t nw = (int64_t)gridDim.x * (blockDim.x / 64);
@@ -240,6 +247,53 @@ __global__ void k_dict_codes(ColRef valid, const uint32_t *__restrict__ slot_of_
         if (i < n) codes[i] = v ? (int32_t)rank_of_slot[slot_of_row[i]] : 0;
         const uint64_t vb = __ballot(v);
         if (lane == 0 && out_valid) out_valid[w] = vb;
+    }
+}
+
+// Join probe side: the code of every probe row whose string the finished table of the build column
+// holds; every other row (NULL, or a string the build side lacks) gets 0 and a cleared validity bit.
+// The table is read-only here (a launch of its own after the insert loop has ended): plain loads, no
+// atomics, no writes.  Same hash, mask and home slot as k_dict_insert.  The walk stops at an empty
+// word or after kDictMaxProbe steps: k_dict_insert placed every stored string within kDictMaxProbe
+// steps of its home slot over words that were all occupied by then, and no slot is ever vacated, so
+// a string not met on the way to the first empty word, or within the bound, is not in the table.
+// No per-workgroup LDS hint table as in k_dict_insert: with 1e6 build strings it was no faster
+// (14.37 ms against 14.24 ms per 1e8 probe rows, DESIGN.md §5 "Utf8 join keys").
+__global__ __launch_bounds__(kBlock) void k_dict_lookup(DictIn probe, int64_t n, DictIn build,
+                                                        const uint64_t *__restrict__ table, int cap_log2, uint64_t hash_mask,
+                                                        const uint64_t *__restrict__ dense, int32_t *__restrict__ codes,
+                                                        uint64_t *__restrict__ out_valid) {
+    const int lane = threadIdx.x & 63;
+    const uint32_t cap_mask = (uint32_t)((1ull << cap_log2) - 1ull);
+    const int64_t nw = (int64_t)gridDim.x * (kBlock / 64);
+    for (int64_t w = (int64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6); w * 64 < n; w += nw) {
+        const int64_t i = w * 64 + lane;
+        bool found = false;
+        int32_t code = 0;
+        if (i < n && col_valid(probe.valid, i)) {
+            const int32_t s = probe.offs[i], len = probe.offs[i + 1] - s;
+            const uint8_t *p = probe.data + s;
+            const uint64_t h = str_hash(p, len) & hash_mask;
+            const uint32_t tag = (uint32_t)(h >> 32);
+            uint32_t idx = (uint32_t)((h * 0x9E3779B97F4A7C15ull) >> (64 - cap_log2));
+            for (int step = 0; step < kDictMaxProbe; ++step) {
+                const uint64_t t = table[idx];
+                if (t == 0) break;
+                if ((uint32_t)(t >> 32) == tag) {
+                    const int64_t r = (int64_t)(uint32_t)t - 1;
+                    const int32_t rs = build.offs[r];
+                    if (build.offs[r + 1] - rs == len && str_eq(p, build.data + rs, len)) {
+                        found = true;
+                        code = (int32_t)dense[idx];
+                        break;
+                    }
+                }
+                idx = (idx + 1u) & cap_mask;
+            }
+        }
+        if (i < n) codes[i] = code;
+        const uint64_t vb = __ballot(found);
+        if (lane == 0) out_valid[w] = vb;
     }
 }
 
@@ -339,28 +393,48 @@ static int order_representatives(qeh_ctx *ctx, const DictIn &in, const uint32_t 
     }
 }
 
-static int utf8_dict_encode(qeh_ctx *ctx, const qeh_column &col, qeh_column *out_codes, qeh_column *out_dict) {
+static int dict_input(const qeh_column &col, const char *who, DictIn *in) {
     QEH_TRY(check_column(col, "utf8 dictionary"));
-    if (col.dtype != QEH_DT_UTF8) return fail(QEH_E_INVALID, "qeh_utf8_dict_encode: the column is not Utf8");
-    const int64_t n = col.length;
+    if (col.dtype != QEH_DT_UTF8) return fail(QEH_E_INVALID, std::string(who) + ": the column is not Utf8");
     // representative rows are stored as 32-bit row + 1, slots and ranks as 32-bit words
-    if (n >= (int64_t)0xFFFFFFFFll) return fail(QEH_E_UNSUPPORTED, "utf8 dictionary: more than 2^32-2 rows per column");
-    if (n > 0 && !col.offsets) return fail(QEH_E_INVALID, "qeh_utf8_dict_encode: Utf8 column without offsets");
-    const bool nullable = col.validity != nullptr;
-    DictIn in{};
-    in.valid = make_colref(col);
-    in.offs = col.offsets + col.offset;
-    in.data = (const uint8_t *)col.values;
+    if (col.length >= (int64_t)0xFFFFFFFFll)
+        return fail(QEH_E_UNSUPPORTED, "utf8 dictionary: more than 2^32-2 rows per column");
+    if (col.length > 0 && !col.offsets) return fail(QEH_E_INVALID, std::string(who) + ": Utf8 column without offsets");
+    in->valid = make_colref(col);
+    in->offs = col.offsets + col.offset;
+    in->data = (const uint8_t *)col.values;
+    return QEH_OK;
+}
 
-    DevBuf table, slot_of_row, ctlb;
-    QEH_TRY(ctlb.alloc(ctx, DC_WORDS * 4));
-    uint32_t *ctl = ctlb.as<uint32_t>();
+// The test knobs, read once per call: every kernel of the call then masks its hashes alike.
+struct DictKnobs {
+    int cap_log2;  // first table size
+    uint64_t hash_mask;
+};
+static DictKnobs dict_knobs() {
+    const int hash_bits = env_int("QEH_UTF8_DICT_HASH_BITS", 1, 64, 64);
+    return {env_int("QEH_UTF8_DICT_CAP_LOG2", 4, kDictMaxCapLog2, kDictDefaultCapLog2),
+            hash_bits >= 64 ? ~0ull : (1ull << hash_bits) - 1ull};
+}
+
+// (a) and the scan of (b): the finished table of a column's distinct strings, the slot of every row
+// and the dense id of every occupied slot (`dense` is left empty when there is no string at all).
+struct DictTable {
+    DevBuf table, slot_of_row, ctl, dense;
+    uint64_t cap = 0;
+    int cap_log2 = 0;
+    int64_t distinct = 0;
+};
+
+static int build_dict_table(qeh_ctx *ctx, const DictIn &in, int64_t n, const DictKnobs &knobs, DictTable *dt) {
+    DevBuf &table = dt->table, &slot_of_row = dt->slot_of_row;
+    QEH_TRY(dt->ctl.alloc(ctx, DC_WORDS * 4));
+    uint32_t *ctl = dt->ctl.as<uint32_t>();
     QEH_TRY(slot_of_row.alloc(ctx, (size_t)std::max<int64_t>(n, 1) * 4));
     // a table of 2n slots is never more than half full; below it a half-full table grows
     const int full_log2 = std::min(kDictMaxCapLog2, std::max(4, ceil_log2((uint64_t)std::max<int64_t>(n, 1) * 2)));
-    int cap_log2 = std::min(full_log2, env_int("QEH_UTF8_DICT_CAP_LOG2", 4, kDictMaxCapLog2, kDictDefaultCapLog2));
-    const int hash_bits = env_int("QEH_UTF8_DICT_HASH_BITS", 1, 64, 64);
-    const uint64_t hash_mask = hash_bits >= 64 ? ~0ull : (1ull << hash_bits) - 1ull;
+    int cap_log2 = std::min(full_log2, knobs.cap_log2);
+    const uint64_t hash_mask = knobs.hash_mask;
     uint64_t cap = 0;
     uint32_t distinct = 0;
     int grows = 0;
@@ -396,7 +470,35 @@ static int utf8_dict_encode(qeh_ctx *ctx, const qeh_column &col, qeh_column *out
             cap_log2 = grows >= 2 ? full_log2 : std::min(full_log2, cap_log2 + 4);
         }
     }
-    const int64_t d = (int64_t)distinct;
+    dt->cap = cap;
+    dt->cap_log2 = cap_log2;
+    dt->distinct = (int64_t)distinct;
+    if (distinct == 0) return QEH_OK;  // n == 0 or all NULL
+    DevBuf occ;
+    QEH_TRY(occ.alloc(ctx, (size_t)cap * 4));
+    QEH_TRY(dt->dense.alloc(ctx, (size_t)cap * 8));
+    uint64_t occupied = 0;
+    {
+        KernelTimer kt(ctx, "utf8_dict_compact");
+        hipLaunchKernelGGL(k_dict_occupied, dim3(grid_for(ctx, (int64_t)cap, kBlock * 4, 8)), dim3(kBlock), 0, ctx->stream,
+                           table.as<uint64_t>(), cap, occ.as<uint32_t>());
+    }
+    QEH_TRY(exclusive_scan_u32(ctx, occ.as<uint32_t>(), dt->dense.as<uint64_t>(), (int64_t)cap, &occupied));
+    if ((int64_t)occupied != dt->distinct) return fail(QEH_E_INTERNAL, "utf8 dictionary: slot count mismatch");
+    return QEH_OK;
+}
+
+static int utf8_dict_encode(qeh_ctx *ctx, const qeh_column &col, qeh_column *out_codes, qeh_column *out_dict) {
+    DictIn in{};
+    QEH_TRY(dict_input(col, "qeh_utf8_dict_encode", &in));
+    const int64_t n = col.length;
+    const bool nullable = col.validity != nullptr;
+    DictTable dt;
+    QEH_TRY(build_dict_table(ctx, in, n, dict_knobs(), &dt));
+    DevBuf &table = dt.table, &slot_of_row = dt.slot_of_row, &dense = dt.dense;
+    uint32_t *ctl = dt.ctl.as<uint32_t>();
+    const uint64_t cap = dt.cap;
+    const int64_t d = dt.distinct;
 
     QEH_TRY(alloc_column(ctx, QEH_DT_INT32, n, nullable, out_codes));
     auto bail = [&](int s) {
@@ -414,23 +516,13 @@ static int utf8_dict_encode(qeh_ctx *ctx, const qeh_column &col, qeh_column *out
         return s == QEH_OK ? s : bail(s);
     }
 
-    DevBuf occ, dense, rep_row, sorted_row, rank_of_rep, rank_of_slot;
-    int s = occ.alloc(ctx, (size_t)cap * 4);
-    if (s == QEH_OK) s = dense.alloc(ctx, (size_t)cap * 8);
-    if (s == QEH_OK) s = rep_row.alloc(ctx, (size_t)d * 4);
+    DevBuf rep_row, sorted_row, rank_of_rep, rank_of_slot;
+    int s = rep_row.alloc(ctx, (size_t)d * 4);
     if (s == QEH_OK) s = sorted_row.alloc(ctx, (size_t)d * 4);
     if (s == QEH_OK) s = rank_of_rep.alloc(ctx, (size_t)d * 4);
     if (s == QEH_OK) s = rank_of_slot.alloc(ctx, (size_t)cap * 4);
     if (s != QEH_OK) return bail(s);
     const int gcap = grid_for(ctx, (int64_t)cap, kBlock * 4, 8);
-    uint64_t occupied = 0;
-    {
-        KernelTimer kt(ctx, "utf8_dict_compact");
-        hipLaunchKernelGGL(k_dict_occupied, dim3(gcap), dim3(kBlock), 0, ctx->stream, table.as<uint64_t>(), cap, occ.as<uint32_t>());
-    }
-    s = exclusive_scan_u32(ctx, occ.as<uint32_t>(), dense.as<uint64_t>(), (int64_t)cap, &occupied);
-    if (s != QEH_OK) return bail(s);
-    if ((int64_t)occupied != d) return bail(fail(QEH_E_INTERNAL, "utf8 dictionary: slot count mismatch"));
     {
         KernelTimer kt(ctx, "utf8_dict_compact");
         hipLaunchKernelGGL(k_dict_reps, dim3(gcap), dim3(kBlock), 0, ctx->stream, table.as<uint64_t>(), cap, dense.as<uint64_t>(),
@@ -446,7 +538,7 @@ static int utf8_dict_encode(qeh_ctx *ctx, const qeh_column &col, qeh_column *out
                            rank_of_rep.as<uint32_t>());
         hipLaunchKernelGGL(k_dict_slot_ranks, dim3(gcap), dim3(kBlock), 0, ctx->stream, table.as<uint64_t>(), cap,
                            dense.as<uint64_t>(), rank_of_rep.as<uint32_t>(), rank_of_slot.as<uint32_t>());
-        hipLaunchKernelGGL(k_dict_codes, dim3(grid_for(ctx, (n + 63) / 64, kBlock / 64, 8)), dim3(kBlock), 0, ctx->stream, in.valid,
+        hipLaunchKernelGGL(k_dict_codes<uint32_t>, dim3(grid_for(ctx, (n + 63) / 64, kBlock / 64, 8)), dim3(kBlock), 0, ctx->stream, in.valid,
                            slot_of_row.as<uint32_t>(), rank_of_slot.as<uint32_t>(), n, (int32_t *)out_codes->values,
                            (uint64_t *)out_codes->validity);
     }
@@ -464,6 +556,58 @@ static int utf8_dict_encode(qeh_ctx *ctx, const qeh_column &col, qeh_column *out
     qeh_column_release(ctx, &perm);
     if (s != QEH_OK) return bail(s);
     out_codes->null_count = nullable ? col.null_count : 0;
+    return QEH_OK;
+}
+
+int utf8_join_encode(qeh_ctx *ctx, const qeh_column &build, const qeh_column &probe, qeh_column *out_build_codes,
+                     qeh_column *out_probe_codes, int64_t *out_distinct) {
+    DictIn bin{}, pin{};
+    QEH_TRY(dict_input(build, "qeh_utf8_join_encode", &bin));
+    QEH_TRY(dict_input(probe, "qeh_utf8_join_encode", &pin));
+    const int64_t nb = build.length, np = probe.length;
+    const DictKnobs knobs = dict_knobs();
+    DictTable dt;
+    QEH_TRY(build_dict_table(ctx, bin, nb, knobs, &dt));
+    const int64_t d = dt.distinct;
+
+    QEH_TRY(alloc_column(ctx, QEH_DT_INT32, nb, build.validity != nullptr, out_build_codes));
+    int s = alloc_column(ctx, QEH_DT_INT32, np, true, out_probe_codes);
+    if (s != QEH_OK) {
+        qeh_column_release(ctx, out_build_codes);
+        return s;
+    }
+    if (d == 0) {  // no build string: nothing matches
+        bool ok = hipMemsetAsync(out_probe_codes->values, 0, (size_t)std::max<int64_t>(np, 1) * 4, ctx->stream) == hipSuccess &&
+                  hipMemsetAsync(out_probe_codes->validity, 0, (size_t)std::max<int64_t>((np + 63) / 64, 1) * 8, ctx->stream) ==
+                      hipSuccess;
+        if (ok && nb > 0)  // all NULL, so the column has a bitmap
+            ok = hipMemsetAsync(out_build_codes->values, 0, (size_t)nb * 4, ctx->stream) == hipSuccess &&
+                 hipMemsetAsync(out_build_codes->validity, 0, (size_t)((nb + 63) / 64) * 8, ctx->stream) == hipSuccess;
+        if (!ok) s = fail(QEH_E_HIP, "utf8 join dictionary: memset failed");
+    } else {
+        {
+            KernelTimer kt(ctx, "utf8_dict_codes");
+            hipLaunchKernelGGL(k_dict_codes<uint64_t>, dim3(grid_for(ctx, (nb + 63) / 64, kBlock / 64, 8)), dim3(kBlock), 0,
+                               ctx->stream, bin.valid, dt.slot_of_row.as<uint32_t>(), dt.dense.as<uint64_t>(), nb,
+                               (int32_t *)out_build_codes->values, (uint64_t *)out_build_codes->validity);
+        }
+        if (np > 0) {
+            KernelTimer kt(ctx, "utf8_dict_lookup");
+            hipLaunchKernelGGL(k_dict_lookup, dim3(grid_for(ctx, (np + 63) / 64, kBlock / 64, 8)), dim3(kBlock), 0, ctx->stream,
+                               pin, np, bin, dt.table.as<uint64_t>(), dt.cap_log2, knobs.hash_mask, dt.dense.as<uint64_t>(),
+                               (int32_t *)out_probe_codes->values, (uint64_t *)out_probe_codes->validity);
+        }
+        if (hipGetLastError() != hipSuccess) s = fail(QEH_E_HIP, "utf8 join dictionary: launch failed");
+    }
+    // the table and the dense ids are freed on return
+    if (hipStreamSynchronize(ctx->stream) != hipSuccess && s == QEH_OK) s = fail(QEH_E_HIP, "utf8 join dictionary failed");
+    if (s != QEH_OK) {
+        qeh_column_release(ctx, out_build_codes);
+        qeh_column_release(ctx, out_probe_codes);
+        return s;
+    }
+    out_build_codes->null_count = build.validity ? build.null_count : 0;
+    if (out_distinct) *out_distinct = d;
     return QEH_OK;
 }
 
@@ -516,4 +660,12 @@ extern "C" int qeh_utf8_dict_encode(qeh_ctx *ctx, const qeh_column *col, qeh_col
     if (!ctx || !col || !out_codes || !out_dict) return fail(QEH_E_INVALID, "qeh_utf8_dict_encode: bad argument");
     DeviceGuard dg(ctx->device);
     return utf8_dict_encode(ctx, *col, out_codes, out_dict);
+}
+
+extern "C" int qeh_utf8_join_encode(qeh_ctx *ctx, const qeh_column *build, const qeh_column *probe,
+                                    qeh_column *out_build_codes, qeh_column *out_probe_codes, int64_t *out_distinct) {
+    if (!ctx || !build || !probe || !out_build_codes || !out_probe_codes)
+        return fail(QEH_E_INVALID, "qeh_utf8_join_encode: bad argument");
+    DeviceGuard dg(ctx->device);
+    return utf8_join_encode(ctx, *build, *probe, out_build_codes, out_probe_codes, out_distinct);
 }

@@ -166,6 +166,13 @@ struct Utf8Keys {
     int decode(int key, qeh_column *col) const;
 };
 int encode_utf8_keys(qeh_ctx *ctx, const qeh_column *keys, int n_keys, Utf8Keys *out);
+// Utf8 equi-join keys (qeh_utf8_join_encode): INT32 codes of both columns from one dictionary built
+// over `build`.  Equal codes <=> equal bytes; codes are dense in [0, *out_distinct) and unordered; a
+// probe row that is NULL or whose string the build side lacks comes out NULL.  Both outputs are owned.
+int utf8_join_encode(qeh_ctx *ctx, const qeh_column &build, const qeh_column &probe, qeh_column *out_build_codes,
+                     qeh_column *out_probe_codes, int64_t *out_distinct);
+// arrow's display name of a column type, as its error messages print it (k_utf8.hip)
+const char *arrow_type_name(int dt);
 inline bool any_utf8(const qeh_column *cols, int n) {
     for (int i = 0; cols && i < n; ++i)
         if (cols[i].dtype == QEH_DT_UTF8) return true;

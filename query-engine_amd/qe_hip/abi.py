@@ -81,6 +81,7 @@ SIGNATURES = {
                                  C.POINTER(I64)]),
     "qeh_hash_join_inner": (I, [P, COLP, COLP, I, COLP, COLP, I, COLP, COLP, C.POINTER(I64)]),
     "qeh_hash_join_outer": (I, [P, I, COLP, COLP, I, COLP, COLP, I, COLP, COLP, C.POINTER(I64)]),
+    "qeh_hash_join": (I, [P, I, COLP, COLP, I, COLP, COLP, I, COLP, COLP, C.POINTER(I64)]),
     "qeh_join_filter_aggregate": (I, [P, COLP, I, I, EXPRP, COLP, COLP, I, AGGP, I, COLP, COLP,
                                       C.POINTER(I64)]),
     "qeh_join_filter_aggregate_prelaunch": (I, [P, COLP, I, I, EXPRP, AGGP, I, C.POINTER(I64), C.POINTER(I64)]),
@@ -110,6 +111,7 @@ SIGNATURES = {
     "qeh_fused_items_check": (I, [P, COLP, I, I, EXPRP, AGGP, I]),
     "qeh_join_filter_aggregate_prelaunch_stats": (I, [P, COLP, I, I, EXPRP, AGGP, I, P, I, I]),
     "qeh_utf8_dict_encode": (I, [P, COLP, COLP, COLP]),
+    "qeh_utf8_join_encode": (I, [P, COLP, COLP, COLP, COLP, C.POINTER(I64)]),
     "qeh_sort_indices": (I, [P, COLP, I, C.POINTER(C.c_int8), COLP]),
     "qeh_sort_indices_nulls": (I, [P, COLP, I, C.POINTER(C.c_int8), C.POINTER(C.c_int8), COLP]),
     "qeh_concat": (I, [P, COLP, I, COLP]),

@@ -338,13 +338,22 @@ class Context:
 
     def hash_join_outer(self, join_type: int, left_key: DeviceColumn, left_cols: Sequence[DeviceColumn],
                         right_key: DeviceColumn, right_cols: Sequence[DeviceColumn]):
-        """qeh_hash_join_outer: join_type 1 LEFT, 2 RIGHT, 3 FULL (0 INNER)."""
+        """qeh_hash_join_outer: join_type 1 LEFT, 2 RIGHT, 3 FULL (0 INNER); Int32 / Int64 keys."""
+        return self._join(self.lib.qeh_hash_join_outer, join_type, left_key, left_cols, right_key, right_cols)
+
+    def hash_join(self, join_type: int, left_key: DeviceColumn, left_cols: Sequence[DeviceColumn],
+                  right_key: DeviceColumn, right_cols: Sequence[DeviceColumn]):
+        """qeh_hash_join: join_type 0 INNER, 1 LEFT, 2 RIGHT, 3 FULL; Int32 / Int64 keys, or two Utf8
+        keys (joined on their shared dictionary codes)."""
+        return self._join(self.lib.qeh_hash_join, join_type, left_key, left_cols, right_key, right_cols)
+
+    def _join(self, fn, join_type, left_key, left_cols, right_key, right_cols):
         cl, cr = self._cols(left_cols), self._cols(right_cols)
         ol = (abi.QehColumn * max(len(left_cols), 1))()
         orr = (abi.QehColumn * max(len(right_cols), 1))()
         rows = C.c_int64()
-        abi.check(self.lib.qeh_hash_join_outer(self.h, int(join_type), C.byref(left_key.c), cl, len(left_cols),
-                                               C.byref(right_key.c), cr, len(right_cols), ol, orr, C.byref(rows)))
+        abi.check(fn(self.h, int(join_type), C.byref(left_key.c), cl, len(left_cols),
+                     C.byref(right_key.c), cr, len(right_cols), ol, orr, C.byref(rows)))
 
         def wrap(c, src):
             d = self._wrap(c)
@@ -622,6 +631,15 @@ class Context:
         codes, dic = abi.QehColumn(), abi.QehColumn()
         abi.check(self.lib.qeh_utf8_dict_encode(self.h, C.byref(col.c), C.byref(codes), C.byref(dic)))
         return self._wrap(codes), self._wrap(dic)
+
+    def utf8_join_encode(self, build: DeviceColumn, probe: DeviceColumn) -> Tuple[DeviceColumn, DeviceColumn, int]:
+        """qeh_utf8_join_encode: (build codes, probe codes, D).  Int32 codes in [0, D) from one
+        dictionary over `build`, equal exactly when the strings are equal (not ordered); a probe
+        row that is NULL or whose string the build side lacks is NULL."""
+        bc, pc, d = abi.QehColumn(), abi.QehColumn(), C.c_int64()
+        abi.check(self.lib.qeh_utf8_join_encode(self.h, C.byref(build.c), C.byref(probe.c), C.byref(bc), C.byref(pc),
+                                                C.byref(d)))
+        return self._wrap(bc), self._wrap(pc), d.value
 
     def sort_indices(self, keys: Sequence[DeviceColumn], ascending: Sequence[bool]) -> DeviceColumn:
         ck = self._cols(keys)

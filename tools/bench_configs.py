@@ -20,12 +20,15 @@
              Int64 column; beside it the same query over the pre-encoded Int32 codes and the
              dictionary encode alone against its floor (offsets + string bytes read, codes written)
   utf8_sort  ORDER BY a Utf8 key: 1e8 rows of all-distinct 16-byte strings; same companions
+  utf8_join  INNER JOIN on a Utf8 key: 1e8 probe rows against 1e6 distinct build strings of 8-24 bytes, 10 %
+             of the probe rows absent; the shared-dictionary encode split into insert and lookup, the lookup
+             against its floor, and the same join over codes encoded ahead of time
   cfg4leg    config 4's per-rank device leg at N = 8 (fused filter + 8-way exchange pass over 1e9
              rows, the dim shard's exchange pass, the local join of what the rank receives)
 
 Prints one JSON line per config: rows/s, ms per run, algorithmic GB/s and
 fraction of 8 TB/s, and the oracle's rows/s on a bounded sample (1 thread).
-usage: python tools/bench_configs.py [--only cfg2,cfg3,cfg5,window,filter,limit,plan,left,full,merge,encode,partition,utf8_groupby,utf8_sort] [--scale 1.0]
+usage: python tools/bench_configs.py [--only cfg2,cfg3,cfg5,window,filter,limit,plan,left,full,merge,encode,partition,utf8_groupby,utf8_sort,utf8_join] [--scale 1.0]
 """
 import argparse
 import json
@@ -774,6 +777,63 @@ def cfg_utf8_sort(ctx, scale):
                     ["radix_pass", "sort_encode"], reps=3)
 
 
+def cfg_utf8_join(ctx, scale):
+    """SELECT ... FROM probe JOIN build ON probe.s = build.s: 1e8 probe rows against 1e6 distinct build
+    strings of 8-24 bytes, about 10 % of the probe rows absent from the build side."""
+    n, nb = int(1e8 * scale), max(int(1e6 * scale), 16)
+    npool = nb + nb // 9  # the probe draws from the build strings and 1/9 as many others: 10 % absent
+    r = np.random.default_rng(SEED)
+    lens = r.integers(8, 25, npool).astype(np.int64)
+    offs = np.zeros(npool + 1, np.int64)
+    np.cumsum(lens, out=offs[1:])
+    data = r.integers(97, 123, int(offs[-1]), dtype=np.uint8)
+    hexd = np.frombuffer(b"0123456789abcdef", np.uint8)
+    ids = np.arange(npool, dtype=np.uint64)[:, None] >> np.arange(28, -4, -4, dtype=np.uint64)
+    data[(offs[:-1, None] + np.arange(8)).ravel()] = hexd[(ids & np.uint64(15)).astype(np.intp)].ravel()  # distinct
+    offs32 = offs.astype(np.int32)
+    pool = upload_utf8_raw(ctx, offs32, data)
+    build = upload_utf8_raw(ctx, offs32[:nb + 1], data[:offs[nb]])
+    probe = ctx.take(pool, ctx.generate(abi.GEN_UNIFORM_MOD, SEED, 2, n, npool))  # gathered on the device
+    pv = ctx.generate(abi.GEN_UNIFORM_MOD, SEED, 4, n, 2 ** 21, lo=-(2 ** 20))
+    bv = ctx.generate(abi.GEN_UNIFORM_MOD, SEED, 5, nb, 2 ** 21, lo=-(2 ** 20))
+    enc_names = ["utf8_dict_insert", "utf8_dict_lookup", "utf8_dict_compact", "utf8_dict_codes", "scan"]
+
+    def enc():
+        b, p, _ = ctx.utf8_join_encode(build, probe)
+        b.release()
+        p.release()
+    enc_wall, enc_kt, _ = timed(ctx, enc, 5, enc_names)
+    bc, pc, d = ctx.utf8_join_encode(build, probe)
+    join_names = ["join_build", "join_count", "join_probe", "join_gather", "join_mat"]
+
+    def joined(res):
+        for c in res[0] + res[1]:
+            c.release()
+        return res[2]
+    wall_u, kt_u, rows = timed(ctx, lambda: joined(ctx.hash_join(0, probe, [pv], build, [bv])), 5, enc_names + join_names)
+    wall_c, kt_c, _ = timed(ctx, lambda: joined(ctx.hash_join_inner(pc, [pv], bc, [bv])), 5, join_names)
+
+    def dict_enc():  # k_dict_insert over the probe column itself: the per-row yardstick of the lookup
+        c, dic = ctx.utf8_dict_encode(probe)
+        c.release()
+        dic.release()
+    _, ins_kt, _ = timed(ctx, dict_enc, 2, ["utf8_dict_insert"])
+    probe_bytes = float(probe.c.values_bytes)
+    alg = 4.0 * (n + 1) + probe_bytes + 4.0 * n + n / 8.0  # probe offsets + bytes read, codes + validity written
+    floor_ms = alg / (PEAK * 1e9) * 1e3
+    lookup_ms = enc_kt["utf8_dict_lookup"]
+    line("utf8 join 1e8 probe rows, 1e6 build strings of 8-24 B, 10 % absent", n, wall_u, alg, lookup_ms, "k_dict_lookup", None,
+         {"build_rows": nb, "distinct": d, "joined_rows": rows, "probe_string_bytes": probe_bytes,
+          "encode_wall_ms": enc_wall * 1e3, "encode_kernel_ms": sum(enc_kt.values()), "encode_kernels_ms": enc_kt,
+          "lookup_floor_ms": floor_ms, "lookup_frac_of_floor": floor_ms / lookup_ms if lookup_ms else None,
+          "lookup_ns_per_row": lookup_ms * 1e6 / n, "insert_ns_per_build_row": enc_kt["utf8_dict_insert"] * 1e6 / nb,
+          "insert_over_probe_column_ms": ins_kt["utf8_dict_insert"],
+          "insert_over_probe_column_ns_per_row": ins_kt["utf8_dict_insert"] * 1e6 / n,
+          "utf8_join_wall_ms": wall_u * 1e3, "utf8_join_kernels_ms": kt_u,
+          "int32_codes_join_wall_ms": wall_c * 1e3, "int32_codes_join_kernels_ms": kt_c,
+          "encode_share_of_join_wall": enc_wall / wall_u})
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--only", default="cfg2,cfg3,cfg5,filter")
@@ -789,7 +849,7 @@ def main():
          "plan": cfg_plan, "left": lambda c, s: cfg_outer(c, s, 1), "full": lambda c, s: cfg_outer(c, s, 3),
          "merge": cfg_merge, "encode": cfg_encode, "shapes": cfg_metric_shapes, "partition": cfg_partition, "cfg3w": cfg3_wide, "window": cfg_window,
          "cfg4leg": cfg4_leg, "cfg4items": cfg4_items_leg, "cfg5leg": cfg5_leg,
-         "window_lsd": cfg_window_lsd, "utf8_groupby": cfg_utf8_groupby, "utf8_sort": cfg_utf8_sort}[name](ctx, args.scale)
+         "window_lsd": cfg_window_lsd, "utf8_groupby": cfg_utf8_groupby, "utf8_sort": cfg_utf8_sort, "utf8_join": cfg_utf8_join}[name](ctx, args.scale)
         ctx.sync()
         abi.check(ctx.lib.qeh_pool_trim(ctx.h))
     ctx.close()
