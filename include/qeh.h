@@ -483,6 +483,15 @@ int qeh_utf8_join_encode(qeh_ctx *ctx, const qeh_column *build, const qeh_column
 int qeh_sort_indices(qeh_ctx *ctx, const qeh_column *keys, int n_keys, const int8_t *ascending,
                      qeh_column *out_perm);
 
+/* The first `limit` entries of the permutation qeh_sort_indices(keys, n_keys, ascending) returns:
+ * exactly those row ids, in that order (stable: ties by input position; NULLs first; floats
+ * totalOrder; Utf8 byte-wise through dictionary codes), without sorting the remaining rows.
+ * out_perm: UINT32, length min(limit, n).  limit == 0 or n == 0: an empty column.
+ * limit >= n: the whole permutation.  limit < 0: QEH_E_INVALID.
+ * Key checks and errors are those of qeh_sort_indices. */
+int qeh_sort_indices_limit(qeh_ctx *ctx, const qeh_column *keys, int n_keys, const int8_t *ascending,
+                           int64_t limit, qeh_column *out_perm);
+
 /* qeh_sort_indices with arrow SortOptions.nulls_first per key (nulls_first NULL: all first),
  * as Merge::sorted passes it (crates/query-distributed/src/operators.rs:97-104,163-172). */
 int qeh_sort_indices_nulls(qeh_ctx *ctx, const qeh_column *keys, int n_keys, const int8_t *ascending,

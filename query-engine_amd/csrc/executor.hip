@@ -1304,12 +1304,51 @@ class Executor {
         return QEH_OK;
     }
 
+    // Limit(Sort(X)) -- ORDER BY ... LIMIT: the first `cap` rows of the sorted input through
+    // qeh_sort_indices_limit (a select instead of the full sort), what sort() then limit() produce
+    int sort_limit(const qeh_plan_node &nd, int64_t cap, Table *out, int depth) {
+        Table in;
+        QEH_TRY(run(nd.input, &in, depth + 1));
+        if (in.rows == 0) {
+            *out = in;
+            return QEH_OK;
+        }
+        std::vector<Col> keys;
+        for (int i = 0; i < nd.n_exprs; ++i) {
+            Col c;
+            QEH_TRY(eval(in, nd.exprs[i], &c));
+            keys.push_back(c);
+        }
+        std::vector<qeh_column> kc;
+        for (auto &c : keys) kc.push_back(c.c);
+        std::vector<int8_t> asc(nd.n_exprs, 1);
+        for (int i = 0; i < nd.n_exprs; ++i)
+            if (nd.ascending) asc[i] = nd.ascending[i];
+        qeh_column perm{};
+        QEH_TRY(qeh_sort_indices_limit(ctx_, kc.data(), (int)kc.size(), asc.data(), cap, &perm));
+        Col p = own(ctx_, perm);
+        out->fields = in.fields;
+        out->cols.clear();
+        for (auto &c : in.cols) {
+            qeh_column g{};
+            QEH_TRY(qeh_take(ctx_, &c.c, &p.c, &g));
+            out->cols.push_back(own(ctx_, g));
+        }
+        out->rows = std::min<int64_t>(cap, in.rows);
+        out->batches = in.batches;
+        return QEH_OK;
+    }
+
     int limit(const qeh_plan_node &nd, Table *out, int depth) {
         Table in;
         const qeh_plan_node &child = plan_->nodes[nd.input];
-        const int64_t cap = nd.fetch >= 0 && !std::getenv("QEH_NO_FUSION")
-                                ? std::max<int64_t>(nd.skip, 0) + nd.fetch : -1;
-        if (cap >= 0 && child.kind == QEH_PLAN_FILTER) {  // Limit(Filter(X)): stop at skip + fetch rows
+        const int64_t skip0 = std::max<int64_t>(nd.skip, 0);
+        // (skip + fetch past int64: no cap, every row is within it)
+        const int64_t cap = nd.fetch >= 0 && nd.fetch <= INT64_MAX - skip0 && !std::getenv("QEH_NO_FUSION")
+                                ? skip0 + nd.fetch : -1;
+        if (cap >= 0 && child.kind == QEH_PLAN_SORT && child.n_exprs > 0) {
+            QEH_TRY(sort_limit(child, cap, &in, depth + 1));
+        } else if (cap >= 0 && child.kind == QEH_PLAN_FILTER) {  // Limit(Filter(X)): stop at skip + fetch rows
             Table x;
             QEH_TRY(run(child.input, &x, depth + 2));
             std::vector<int32_t> idx(x.cols.size());
@@ -1322,7 +1361,7 @@ class Executor {
         }
         const int64_t start = std::min<int64_t>(std::max<int64_t>(nd.skip, 0), in.rows);
         int64_t end = in.rows;
-        if (nd.fetch >= 0) end = std::min<int64_t>(end, start + nd.fetch);
+        if (nd.fetch >= 0 && nd.fetch < end - start) end = start + nd.fetch;
         *out = in;
         for (auto &c : out->cols) {  // zero-copy slice (RecordBatch::slice)
             c.c.offset += start;

@@ -1635,6 +1635,46 @@ __global__ void k_u64_to_u32_idx(const int64_t *__restrict__ in, int64_t n, int6
     }
 }
 
+// ---- entry points for the top-k select (k_topk.hip) -------------------------------------------
+__global__ void k_perm_prefix(const uint32_t *__restrict__ perm, const uint32_t *__restrict__ rows, int64_t m,
+                              uint32_t *__restrict__ out) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < m; i += (int64_t)gridDim.x * blockDim.x)
+        out[i] = rows ? rows[perm[i]] : perm[i];
+}
+
+int sort_check_keys(const qeh_column *keys, int n_keys, int64_t *n) { return check_sort_keys(keys, n_keys, n); }
+
+int sort_key_range(qeh_ctx *ctx, const qeh_column &col, int64_t *mn, int64_t *mx) {
+    DevBuf st;
+    QEH_TRY(st.alloc(ctx, sizeof(KeyStats)));
+    {
+        KernelTimer kt(ctx, "sort_encode");
+        hipLaunchKernelGGL(k_stats_init, dim3(1), dim3(1), 0, ctx->stream, st.as<KeyStats>());
+        hipLaunchKernelGGL(k_key_stats, dim3(grid_for(ctx, col.length, kBlock * 8, 1)), dim3(kBlock), 0, ctx->stream,
+                           make_colref(col), nullptr, col.length, st.as<KeyStats>());
+    }
+    QEH_HIP(hipGetLastError());
+    KeyStats ks{};
+    QEH_TRY(read_small(ctx, &ks, st.p, sizeof ks));
+    *mn = ks.mn, *mx = ks.mx;
+    return QEH_OK;
+}
+
+int sort_perm_prefix(qeh_ctx *ctx, const qeh_column *keys, int n_keys, const int8_t *ascending, int64_t n, int64_t limit,
+                     const uint32_t *rows, qeh_column *out_perm) {
+    RadixState rs;
+    QEH_TRY(sort_perm(ctx, keys, n_keys, ascending, n, rs));
+    const int64_t m = std::min(limit, n);
+    QEH_TRY(alloc_column(ctx, QEH_DT_UINT32, m, false, out_perm));
+    if (m > 0) {
+        hipLaunchKernelGGL(k_perm_prefix, dim3(grid_for(ctx, m, kBlock * 8, 8)), dim3(kBlock), 0, ctx->stream,
+                           rs.v[rs.cur].as<uint32_t>(), rows, m, (uint32_t *)out_perm->values);
+        QEH_HIP(hipGetLastError());
+    }
+    QEH_HIP(hipStreamSynchronize(ctx->stream));  // rs's buffers return to the pool with this call
+    return QEH_OK;
+}
+
 }  // namespace qeh
 
 using namespace qeh;

@@ -80,6 +80,14 @@ int sort_pairs_payload_parts(qeh_ctx *ctx, const qeh_column *keys, const qeh_col
                              bool nulls_first, qeh_column *out_key, qeh_column *out_val);
 int sort_pairs_payload(qeh_ctx *ctx, const qeh_column &key, const qeh_column &val, bool asc, bool nulls_first,
                        qeh_column *out_key, qeh_column *out_val);
+// What the top-k select (k_topk.hip) needs of the sort (k_sort.hip): qeh_sort_indices' key checks;
+// min / max of a key column's ordered values over its non-NULL rows (mn > mx: none; one synchronous
+// read); and the first min(limit, n) entries of the stable sort permutation of `keys` as a fresh
+// UINT32 column, mapped through rows[] when given (the keys are then those of rows rows[0..n)).
+int sort_check_keys(const qeh_column *keys, int n_keys, int64_t *n);
+int sort_key_range(qeh_ctx *ctx, const qeh_column &col, int64_t *mn, int64_t *mx);
+int sort_perm_prefix(qeh_ctx *ctx, const qeh_column *keys, int n_keys, const int8_t *ascending, int64_t n, int64_t limit,
+                     const uint32_t *rows, qeh_column *out_perm);
 // min / max / valid count of an integer column (one synchronous read).
 int column_minmax(qeh_ctx *ctx, const qeh_column &col, int64_t *mn, int64_t *mx, int64_t *valid);
 // min / max / valid count of several integer columns, one synchronous read.

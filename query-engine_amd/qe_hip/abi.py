@@ -113,7 +113,8 @@ SIGNATURES = {
     "qeh_utf8_dict_encode": (I, [P, COLP, COLP, COLP]),
     "qeh_utf8_join_encode": (I, [P, COLP, COLP, COLP, COLP, C.POINTER(I64)]),
     "qeh_sort_indices": (I, [P, COLP, I, C.POINTER(C.c_int8), COLP]),
-    "qeh_sort_indices_nulls": (I, [P, COLP, I, C.POINTER(C.c_int8), C.POINTER(C.c_int8), COLP]),
+    "qeh_sort_indices_limit": (I, [P, COLP, I, C.POINTER(C.c_int8), C.c_int64, COLP]),
+    "qeh_sort_indices_nulls":(I, [P, COLP, I, C.POINTER(C.c_int8), C.POINTER(C.c_int8), COLP]),
     "qeh_concat": (I, [P, COLP, I, COLP]),
     "qeh_merge_sorted": (I, [P, COLP, I, I, C.POINTER(C.c_int32), C.POINTER(C.c_int8), C.POINTER(C.c_int8), I, COLP,
                              C.POINTER(I64)]),

@@ -648,6 +648,14 @@ class Context:
         abi.check(self.lib.qeh_sort_indices(self.h, ck, len(keys), asc, C.byref(out)))
         return self._wrap(out)
 
+    def sort_indices_limit(self, keys: Sequence[DeviceColumn], ascending: Sequence[bool], limit: int) -> DeviceColumn:
+        """qeh_sort_indices_limit: the first `limit` row ids of sort_indices(keys, ascending)."""
+        ck = self._cols(keys)
+        asc = (C.c_int8 * max(len(keys), 1))(*[1 if a else 0 for a in ascending])
+        out = abi.QehColumn()
+        abi.check(self.lib.qeh_sort_indices_limit(self.h, ck, len(keys), asc, limit, C.byref(out)))
+        return self._wrap(out)
+
     def sort_indices_nulls(self, keys: Sequence[DeviceColumn], ascending: Sequence[bool],
                            nulls_first: Sequence[bool]) -> DeviceColumn:
         ck = self._cols(keys)

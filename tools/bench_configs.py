@@ -23,12 +23,15 @@
   utf8_join  INNER JOIN on a Utf8 key: 1e8 probe rows against 1e6 distinct build strings of 8-24 bytes, 10 %
              of the probe rows absent; the shared-dictionary encode split into insert and lookup, the lookup
              against its floor, and the same join over codes encoded ahead of time
+  topk       ORDER BY k LIMIT 100 over 1e8 rows (spread Int64, Float64, Int64 in [0, 1024)): the radix-select
+             path of qeh_sort_indices_limit against the full sort in the same process, then the limit / n, n and
+             candidate-share sweeps behind its fallback constants
   cfg4leg    config 4's per-rank device leg at N = 8 (fused filter + 8-way exchange pass over 1e9
              rows, the dim shard's exchange pass, the local join of what the rank receives)
 
 Prints one JSON line per config: rows/s, ms per run, algorithmic GB/s and
 fraction of 8 TB/s, and the oracle's rows/s on a bounded sample (1 thread).
-usage: python tools/bench_configs.py [--only cfg2,cfg3,cfg5,window,filter,limit,plan,left,full,merge,encode,partition,utf8_groupby,utf8_sort,utf8_join] [--scale 1.0]
+usage: python tools/bench_configs.py [--only cfg2,cfg3,cfg5,window,filter,limit,plan,left,full,merge,encode,partition,utf8_groupby,utf8_sort,utf8_join,topk] [--scale 1.0]
 """
 import argparse
 import json
@@ -834,6 +837,80 @@ def cfg_utf8_join(ctx, scale):
           "encode_share_of_join_wall": enc_wall / wall_u})
 
 
+TOPK_KERNELS = ["topk_select", "radix_pass", "sort_encode", "gather", "scan"]
+
+
+def topk_ab(ctx, key, limit, reps, select_env):
+    """qeh_sort_indices_limit with the select path (`select_env` set) and with the full sort
+    (QEH_NO_TOPK=1), interleaved in this process: per side the median wall ms and the kernel ms per
+    call by timer name."""
+    sides = {"select": select_env, "full": {"QEH_NO_TOPK": "1"}}
+    knobs = ["QEH_NO_TOPK", "QEH_TOPK_FORCE", "QEH_TOPK_MIN_ROWS"]
+    wall = {s: [] for s in sides}
+    kms = {s: dict.fromkeys(TOPK_KERNELS, 0.0) for s in sides}
+    ctx.timing(True)
+    for rep in range(reps + 1):  # rep 0 warms both sides up
+        for side, env in sides.items():
+            for kn in knobs:
+                os.environ.pop(kn, None)
+            os.environ.update(env)
+            ctx.timing_reset()
+            ctx.sync()
+            t0 = time.perf_counter()
+            ctx.sort_indices_limit([key], [True], limit).release()
+            ctx.sync()
+            dt = time.perf_counter() - t0
+            if rep:
+                wall[side].append(dt * 1e3)
+                for kn in TOPK_KERNELS:
+                    kms[side][kn] += ctx.kernel_time(kn)[0] / reps
+    ctx.timing(False)
+    for kn in knobs:
+        os.environ.pop(kn, None)
+    return {s: float(np.median(wall[s])) for s in sides}, kms
+
+
+def cfg_topk(ctx, scale):
+    """SELECT ... ORDER BY k LIMIT 100 over 1e8 rows: qeh_sort_indices_limit's select path against
+    the full sort cut to 100 rows (QEH_NO_TOPK=1), same process, interleaved; then the sweeps the
+    three fallback constants of csrc/k_topk.hip are read from (QEH_TOPK_FORCE=1: the select path at
+    any limit, row count and candidate share)."""
+    n = int(1e8 * scale)
+    keys = {"int64 spread over 2^62": lambda m: ctx.generate(abi.GEN_UNIFORM_MOD, SEED, 2, m, 2 ** 62, lo=-(2 ** 61)),
+            "float64 in [0, 1)": lambda m: ctx.generate(abi.GEN_UNIT_F64, SEED, 3, m),
+            "int64 in [0, 1024) (heavy ties)": lambda m: ctx.generate(abi.GEN_UNIFORM_MOD, SEED, 4, m, 1024)}
+    for name, gen in keys.items():
+        key = gen(n)
+        wall, kms = topk_ab(ctx, key, 100, 5, {})
+        sel_ms = kms["select"]["topk_select"]
+        taken = sel_ms > 0 and kms["select"]["radix_pass"] < 0.5 * kms["full"]["radix_pass"]
+        line(f"topk ORDER BY k LIMIT 100, {n} rows, {name}", n, wall["select"] * 1e-3, None, sel_ms, "k_topk_hist", None,
+             {"select_wall_ms": wall["select"], "full_sort_wall_ms": wall["full"],
+              "speedup_wall": wall["full"] / wall["select"], "select_path_taken": bool(taken),
+              "select_kernels_ms": kms["select"], "full_sort_kernels_ms": kms["full"],
+              "read_floor_ms_per_pass": 8.0 * n / (PEAK * 1e9) * 1e3,
+              "note": "floor = passes x n x 8 B of key reads; passes = range + select digits + count + write"})
+        del key
+    force = {"QEH_TOPK_FORCE": "1"}
+    for m in [int(x * scale) for x in (1e4, 1e5, 1e6, 2e6, 4e6, 1e7, 1e8)]:  # limit / n and n
+        key = keys["int64 spread over 2^62"](m)
+        for share in (1e-6, 1e-5, 1e-4, 1e-3, 1e-2, 1 / 32, 1 / 16, 1 / 8, 1 / 4, 1 / 2):
+            limit = max(1, int(m * share))
+            wall, _ = topk_ab(ctx, key, limit, 3, force)
+            print(json.dumps({"config": "topk sweep limit/n", "rows": m, "limit": limit, "limit_share": share,
+                              "select_wall_ms": wall["select"], "full_sort_wall_ms": wall["full"],
+                              "speedup_wall": wall["full"] / wall["select"]}), flush=True)
+        del key
+    for m in [int(x * scale) for x in (1e6, 1e8)]:  # candidate share: keys in [0, R), about m / R rows tie at the threshold
+        for r in (2, 4, 8, 16, 32, 64, 128, 256, 512):
+            key = ctx.generate(abi.GEN_UNIFORM_MOD, SEED, 5, m, r)
+            wall, _ = topk_ab(ctx, key, 100, 3, force)
+            print(json.dumps({"config": "topk sweep candidate share", "rows": m, "limit": 100, "cand_share": 1.0 / r,
+                              "select_wall_ms": wall["select"], "full_sort_wall_ms": wall["full"],
+                              "speedup_wall": wall["full"] / wall["select"]}), flush=True)
+            del key
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--only", default="cfg2,cfg3,cfg5,filter")
@@ -849,7 +926,8 @@ def main():
          "plan": cfg_plan, "left": lambda c, s: cfg_outer(c, s, 1), "full": lambda c, s: cfg_outer(c, s, 3),
          "merge": cfg_merge, "encode": cfg_encode, "shapes": cfg_metric_shapes, "partition": cfg_partition, "cfg3w": cfg3_wide, "window": cfg_window,
          "cfg4leg": cfg4_leg, "cfg4items": cfg4_items_leg, "cfg5leg": cfg5_leg,
-         "window_lsd": cfg_window_lsd, "utf8_groupby": cfg_utf8_groupby, "utf8_sort": cfg_utf8_sort, "utf8_join": cfg_utf8_join}[name](ctx, args.scale)
+         "window_lsd": cfg_window_lsd, "utf8_groupby": cfg_utf8_groupby, "utf8_sort": cfg_utf8_sort, "utf8_join": cfg_utf8_join,
+         "topk": cfg_topk}[name](ctx, args.scale)
         ctx.sync()
         abi.check(ctx.lib.qeh_pool_trim(ctx.h))
     ctx.close()
