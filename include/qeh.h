@@ -79,7 +79,8 @@ typedef struct qeh_column {
 /* ---- expressions: postfix encoding of PhysicalExpr ------------------------
  * physical_plan.rs:74-142.  Only the variants the converters emit
  * (crates/query-pgwire/src/backend.rs:727-756) are representable:
- * Column{index}, Literal(ScalarValue), BinaryExpr, UnaryExpr.  Children come
+ * Column{index}, Literal(ScalarValue), BinaryExpr, UnaryExpr -- and, inside a
+ * plan only, the planner's ScalarSubquery / InSubquery / Exists.  Children come
  * before parents (post-order); the last node is the root.  Type coercion is
  * NOT encoded: the library applies the reference's rules
  * (operators.rs:616-709) itself.                                             */
@@ -87,7 +88,18 @@ enum qeh_expr_kind {
     QEH_EX_COLUMN = 1,
     QEH_EX_LITERAL = 2,
     QEH_EX_BINARY = 3,
-    QEH_EX_UNARY = 4
+    QEH_EX_UNARY = 4,
+    /* Uncorrelated subquery expressions (physical_plan.rs:91-104; the reference's planner emits
+     * them, planner.rs:448-456 and :614-621, its executor stubs them, operators.rs:34-52).  They
+     * exist only inside a plan handed to qeh_execute_plan (qeh_plan.h): `index` = the subplan's
+     * root in the same qeh_plan.nodes array, `op` = negated (0 / 1).  IN_SUBQUERY is the postfix
+     * parent of one child, the tested expression; the other two are leaves.  Accepted in Filter
+     * predicates and Projection expressions; anywhere else (join `on`, Sort, group and aggregate
+     * arguments, window expressions, and qeh_filter / qeh_eval / qeh_expr_type called directly)
+     * QEH_E_UNSUPPORTED. */
+    QEH_EX_SCALAR_SUBQUERY = 5, /* one column; 0 rows -> NULL, 1 row -> its value, more -> QEH_E_INVALID */
+    QEH_EX_IN_SUBQUERY = 6,     /* child [NOT] IN (one-column subplan): qeh_in_set's rules            */
+    QEH_EX_EXISTS = 7           /* the subplan returns at least one row, flipped by `op`              */
 };
 /* Same order as `BinaryOp` (physical_plan.rs:119-136; TsMatch excluded). */
 enum qeh_binop {
@@ -100,8 +112,9 @@ enum qeh_unop { QEH_UOP_NOT = 0, QEH_UOP_MINUS = 1 };
 
 typedef struct qeh_expr_node {
     int32_t kind;        /* enum qeh_expr_kind                              */
-    int32_t op;          /* qeh_binop / qeh_unop                            */
-    int32_t index;       /* COLUMN: input column index; UTF8 LITERAL: byte length */
+    int32_t op;          /* qeh_binop / qeh_unop; subquery kinds: negated   */
+    int32_t index;       /* COLUMN: input column index; UTF8 LITERAL: byte length;
+                            subquery kinds: the subplan's root node          */
     int32_t lit_dtype;   /* LITERAL: enum qeh_dtype (NULL = ScalarValue::Null) */
     int32_t lit_is_null; /* LITERAL: typed None (e.g. Int64(None))         */
     int32_t _pad;
@@ -475,6 +488,25 @@ int qeh_utf8_dict_encode(qeh_ctx *ctx, const qeh_column *col, qeh_column *out_co
  * The empty string is a value, not NULL; strings compare as bytes, as k_utf8_cmp does. */
 int qeh_utf8_join_encode(qeh_ctx *ctx, const qeh_column *build, const qeh_column *probe,
                          qeh_column *out_build_codes, qeh_column *out_probe_codes, int64_t *out_distinct);
+
+/* expr [NOT] IN (set): intended semantics of PhysicalExpr::InSubquery, physical_plan.rs:95-99
+ * (the reference's executor stubs it, operators.rs:34-52) -- a semi join (anti join when
+ * `negated`) that yields one bit per probe row instead of pairs.  out: an owned BOOL column of
+ * probe->length rows, SQL three-valued logic:
+ *   set has no rows at all                   -> negated ? TRUE : FALSE, valid, also for NULL probes
+ *   NULL probe (non-empty set)               -> NULL
+ *   found (probe valid)                      -> !negated
+ *   not found (probe valid), set has a NULL  -> NULL
+ *   not found (probe valid), set has no NULL -> negated
+ * Types: Int32 / Int64 on both sides (mixed widths are widened); Float32 against Float32 or Float64
+ * against Float64, compared by value bits (same-bits NaN matches, 0.0 and -0.0 differ); Utf8 against
+ * Utf8 through one shared dictionary (qeh_utf8_join_encode over the set).  Any other pairing is
+ * QEH_E_TYPE with arrow's "Invalid argument error: Invalid comparison operation: X == Y".
+ * Both columns may carry validity bitmaps and non-zero offsets; duplicates in the set are fine.
+ * The set is a bitmap over its key range or a key-only hash set, chosen from the range and the
+ * row count; QEH_IN_SET=bitmap|hash (read per call) forces one for integer and Utf8 keys
+ * (float keys always take the hash set; a forced bitmap over a range beyond 2^31 is QEH_E_INVALID). */
+int qeh_in_set(qeh_ctx *ctx, const qeh_column *probe, const qeh_column *set, int negated, qeh_column *out);
 
 /* Stable lexicographic sort -> permutation (UINT32 row ids) of the input.
  * Intended semantics of `Sort` (physical_plan.rs:40-44; executor.rs:290-297

@@ -16,6 +16,10 @@
  * `arrow::ffi::{FFI_ArrowArray, FFI_ArrowSchema}` import.  Batch boundaries
  * are not semantically visible in the reference except through its
  * "no batches" quirks, which the executor tracks.
+ *
+ * Subquery expressions (qeh_expr_kind 5-7, qeh.h) name their subplan by the
+ * index of its root in the same `nodes` array; the subplan's Scan nodes use
+ * the same `sources` array.  Each subplan runs once per qeh_execute_plan call.
  */
 #ifndef QEH_PLAN_H
 #define QEH_PLAN_H

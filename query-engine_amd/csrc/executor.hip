@@ -14,6 +14,11 @@
 // GROUP BY, INNER equi-join, Sort and ROW_NUMBER follow the intended
 // semantics; Limit slices (executor.rs:299-341); SubqueryScan and IndexScan
 // behave as in the reference (executor.rs:72-88).
+// Subquery expressions (ScalarSubquery / InSubquery / Exists, physical_plan.rs:91-104, stubbed by
+// the reference's executor, operators.rs:34-52) in Filter predicates and Projection expressions are
+// replaced before typing and before the fusion decisions (rewrite_subqueries): the subplan runs
+// once per call through run(), IN becomes a BOOL column from qeh_in_set appended to the operator's
+// inputs, EXISTS a Boolean literal, a scalar subquery a literal (or an all-NULL column).
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
@@ -59,6 +64,22 @@ struct Table {
     std::vector<Col> cols;
     int64_t rows = 0;
     int64_t batches = 0;  // >0 iff the reference would hold at least one batch here
+};
+
+inline bool subquery_kind(int kind) { return kind >= QEH_EX_SCALAR_SUBQUERY && kind <= QEH_EX_EXISTS; }
+inline bool has_subquery(const qeh_expr &e) {
+    for (int i = 0; e.nodes && i < e.n_nodes; ++i)
+        if (subquery_kind(e.nodes[i].kind)) return true;
+    return false;
+}
+
+// An expression with its subquery nodes replaced (rewrite_subqueries): `table` = the operator's
+// input with the temporary columns appended, `expr` reads it.  Owns the host bytes of Utf8 scalars.
+struct SubqRewrite {
+    Table table;
+    std::vector<qeh_expr_node> nodes;
+    qeh_expr expr{};
+    std::vector<std::unique_ptr<std::string>> strs;
 };
 
 Col own(qeh_ctx *ctx, const qeh_column &c) {
@@ -529,6 +550,10 @@ class Executor {
     int run(int node, Table *out, int depth = 0) {
         if (node < 0 || node >= plan_->n_nodes) return fail(QEH_E_INVALID, "plan node index out of range");
         if (depth > 256) return fail(QEH_E_INVALID, "plan too deep (cycle?)");
+        if (!validated_) {
+            QEH_TRY(validate_subqueries());
+            validated_ = true;
+        }
         const qeh_plan_node &nd = plan_->nodes[node];
         switch (nd.kind) {
             case QEH_PLAN_SCAN:
@@ -552,6 +577,273 @@ class Executor {
     const qeh_plan *plan_;
     const qeh_source *src_;
     int n_src_;
+    bool validated_ = false;
+    int subq_depth_ = 0;
+    std::map<int, std::shared_ptr<Table>> subq_;  // subplan root -> its result (run once per call)
+
+    // Subquery kinds are taken in Filter predicates and Projection expressions; every other place
+    // refuses them by name.  Also checks each subquery node's fields.
+    int validate_subqueries() const {
+        auto refuse = [](const qeh_expr &e, const char *place) -> int {
+            if (!has_subquery(e)) return QEH_OK;
+            return fail(QEH_E_UNSUPPORTED, std::string("subquery expression in ") + place +
+                                               " is not supported on the device (Filter predicates and Projection "
+                                               "expressions take one)");
+        };
+        auto accept = [&](const qeh_expr &e) -> int {
+            for (int i = 0; e.nodes && i < e.n_nodes; ++i) {
+                const qeh_expr_node &x = e.nodes[i];
+                if (!subquery_kind(x.kind)) continue;
+                if (x.index < 0 || x.index >= plan_->n_nodes)
+                    return fail(QEH_E_INVALID, "subquery expression: subplan root index out of range");
+                if (x.op != 0 && x.op != 1) return fail(QEH_E_INVALID, "subquery expression: negated must be 0 or 1");
+            }
+            return QEH_OK;
+        };
+        for (int k = 0; k < plan_->n_nodes; ++k) {
+            const qeh_plan_node &nd = plan_->nodes[k];
+            switch (nd.kind) {
+                case QEH_PLAN_FILTER: QEH_TRY(accept(nd.predicate)); break;
+                case QEH_PLAN_PROJECTION:
+                    for (int i = 0; nd.exprs && i < nd.n_exprs; ++i) QEH_TRY(accept(nd.exprs[i]));
+                    break;
+                case QEH_PLAN_HASH_JOIN:
+                    if (nd.has_predicate) QEH_TRY(refuse(nd.predicate, "a join condition"));
+                    break;
+                case QEH_PLAN_SORT:
+                    for (int i = 0; nd.exprs && i < nd.n_exprs; ++i) QEH_TRY(refuse(nd.exprs[i], "a Sort expression"));
+                    break;
+                case QEH_PLAN_HASH_AGGREGATE:
+                    for (int i = 0; nd.exprs && i < nd.n_exprs; ++i) QEH_TRY(refuse(nd.exprs[i], "a GROUP BY expression"));
+                    for (int i = 0; nd.aggs && i < nd.n_aggs; ++i) QEH_TRY(refuse(nd.aggs[i].expr, "an aggregate argument"));
+                    break;
+                case QEH_PLAN_WINDOW:
+                    for (int w = 0; nd.window && w < nd.n_window; ++w) {
+                        const qeh_window_expr &we = nd.window[w];
+                        for (int i = 0; we.args && i < we.n_args; ++i) QEH_TRY(refuse(we.args[i], "a window expression"));
+                        for (int i = 0; we.partition_by && i < we.n_partition; ++i)
+                            QEH_TRY(refuse(we.partition_by[i], "a window expression"));
+                        for (int i = 0; we.order_by && i < we.n_order; ++i)
+                            QEH_TRY(refuse(we.order_by[i], "a window expression"));
+                    }
+                    break;
+                default: break;
+            }
+        }
+        return QEH_OK;
+    }
+
+    // The result of the subplan rooted at `root`, run once per qeh_execute_plan call.
+    int subquery(int root, const Table **out) {
+        auto it = subq_.find(root);
+        if (it == subq_.end()) {
+            if (subq_depth_ >= 16) return fail(QEH_E_INVALID, "subquery expressions nested too deep (cycle?)");
+            auto t = std::make_shared<Table>();
+            ++subq_depth_;
+            const int s = run(root, t.get());
+            --subq_depth_;
+            QEH_TRY(s);
+            it = subq_.emplace(root, t).first;
+        }
+        *out = it->second.get();
+        return QEH_OK;
+    }
+
+    // `n` rows of NULL typed `dt`
+    int null_column(int dt, int64_t n, Col *out) {
+        qeh_column c{};
+        const size_t vbytes = (size_t)((n + 63) / 64) * 8;
+        if (dt == QEH_DT_UTF8) {
+            QEH_TRY(alloc_column(ctx_, QEH_DT_INT32, n + 1, true, &c));  // the offsets, all 0
+            QEH_HIP(hipMemsetAsync(c.values, 0, (size_t)(n + 1) * 4, ctx_->stream));
+            c.offsets = (int32_t *)c.values;
+            c.values = nullptr;
+            c.dtype = QEH_DT_UTF8;
+            c.length = n;
+            void *bytes = nullptr;
+            const int s = ctx_->pool->alloc(8, &bytes);
+            if (s != QEH_OK) {
+                qeh_column_release(ctx_, &c);
+                return s;
+            }
+            c.values = bytes;
+        } else {
+            QEH_TRY(alloc_column(ctx_, dt, n, true, &c));
+            const size_t bytes = dt == QEH_DT_BOOL ? vbytes : (size_t)n * dtype_size(dt);
+            if (bytes) QEH_HIP(hipMemsetAsync(c.values, 0, bytes, ctx_->stream));
+        }
+        QEH_HIP(hipMemsetAsync(c.validity, 0, vbytes ? vbytes : 8, ctx_->stream));
+        c.null_count = n;
+        *out = own(ctx_, c);
+        return QEH_OK;
+    }
+
+    // The type of a scalar subquery whose subplan returned no batch and no schema (a global
+    // aggregate over no input batch, executor.rs:178): COUNT is Int64 and AVG Float64 whatever they
+    // read; a SUM / MIN / MAX takes its input's type, which nothing here knows, and is typed
+    // Float64, which compares with every numeric type (the value is NULL either way).
+    int null_scalar_type(int root) const {
+        int k = root;
+        for (int hops = 0; hops < 64 && k >= 0 && k < plan_->n_nodes; ++hops) {
+            const qeh_plan_node &nd = plan_->nodes[k];
+            if (nd.kind == QEH_PLAN_HASH_AGGREGATE) {
+                if (nd.n_exprs == 0 && nd.n_aggs == 1 && nd.aggs[0].func == QEH_AGG_COUNT) return QEH_DT_INT64;
+                return QEH_DT_FLOAT64;
+            }
+            if (nd.kind == QEH_PLAN_SUBQUERY_SCAN || nd.kind == QEH_PLAN_LIMIT || nd.kind == QEH_PLAN_SORT ||
+                nd.kind == QEH_PLAN_FILTER)
+                k = nd.input;
+            else break;
+        }
+        return QEH_DT_FLOAT64;
+    }
+
+    // ScalarSubquery -> a LITERAL node of the subplan's single value, or (no row, or a NULL value)
+    // an all-NULL column of its type appended to rw->table: a typed None literal would type as Null
+    // (operators.rs:322-347) and fail every comparison instead of yielding NULL.
+    int scalar_subquery(const qeh_expr_node &x, SubqRewrite *rw, qeh_expr_node *node) {
+        const Table *t = nullptr;
+        QEH_TRY(subquery(x.index, &t));
+        const size_t ncols = std::max(t->cols.size(), t->fields.size());
+        if (ncols > 1 || (ncols == 0 && t->batches > 0))
+            return fail(QEH_E_INVALID, "Scalar subquery must return exactly one column");
+        if (t->rows > 1) return fail(QEH_E_INVALID, "Scalar subquery returned more than one row");
+        int dt = t->cols.size() == 1 ? t->cols[0].c.dtype : (t->fields.size() == 1 ? t->fields[0].dtype : null_scalar_type(x.index));
+        if (dt == QEH_DT_UINT32) dt = QEH_DT_INT64;
+        bool null = t->rows == 0 || t->cols.empty();
+        uint64_t bits = 0;
+        std::string bytes;
+        if (!null) {
+            const qeh_column &c = t->cols[0].c;
+            if (c.validity) {
+                uint8_t b = 0;
+                QEH_TRY(read_small(ctx_, &b, c.validity + (c.offset >> 3), 1));
+                null = !((b >> (c.offset & 7)) & 1);
+            }
+            if (!null && c.dtype == QEH_DT_UTF8) {
+                int32_t o[2];
+                QEH_TRY(read_small(ctx_, o, c.offsets + c.offset, 8));
+                if (o[1] < o[0]) return fail(QEH_E_INVALID, "Scalar subquery: malformed Utf8 offsets");
+                bytes.resize((size_t)(o[1] - o[0]));
+                if (!bytes.empty()) QEH_TRY(read_small(ctx_, &bytes[0], (const uint8_t *)c.values + o[0], bytes.size()));
+            } else if (!null && c.dtype == QEH_DT_BOOL) {
+                uint8_t b = 0;
+                QEH_TRY(read_small(ctx_, &b, (const uint8_t *)c.values + (c.offset >> 3), 1));
+                bits = (b >> (c.offset & 7)) & 1;
+            } else if (!null) {
+                const size_t es = dtype_size(c.dtype);
+                QEH_TRY(read_small(ctx_, &bits, (const char *)c.values + (size_t)c.offset * es, es));
+            }
+        }
+        *node = qeh_expr_node{};
+        if (null) {
+            Col nc;
+            QEH_TRY(null_column(dt, rw->table.rows, &nc));
+            rw->table.cols.push_back(nc);
+            rw->table.fields.push_back({"", dt, true});
+            node->kind = QEH_EX_COLUMN;
+            node->index = (int32_t)rw->table.cols.size() - 1;
+            return QEH_OK;
+        }
+        node->kind = QEH_EX_LITERAL;
+        node->lit_dtype = dt;
+        switch (t->cols[0].c.dtype) {
+            case QEH_DT_BOOL: node->lit_i64 = (int64_t)bits; break;
+            case QEH_DT_INT32: node->lit_i64 = (int64_t)(int32_t)(uint32_t)bits; break;
+            case QEH_DT_UINT32: node->lit_i64 = (int64_t)(uint32_t)bits; break;
+            case QEH_DT_INT64: node->lit_i64 = (int64_t)bits; break;
+            case QEH_DT_FLOAT32: {
+                const uint32_t b = (uint32_t)bits;
+                float f;
+                std::memcpy(&f, &b, 4);
+                node->lit_f64 = (double)f;
+                break;
+            }
+            case QEH_DT_FLOAT64: std::memcpy(&node->lit_f64, &bits, 8); break;
+            default:  // Utf8: host bytes, alive as long as the rewrite
+                rw->strs.push_back(std::make_unique<std::string>(bytes));
+                node->index = (int32_t)bytes.size();
+                node->lit_i64 = (int64_t)(uintptr_t)rw->strs.back()->data();
+                break;
+        }
+        return QEH_OK;
+    }
+
+    // InSubquery over the already rewritten child `child`: the BOOL column of qeh_in_set, appended
+    // to rw->table.  A subplan without batches and without schema (the reference's vec![]) is the
+    // empty set.
+    int in_subquery(const qeh_expr_node &x, const qeh_expr &child, SubqRewrite *rw, qeh_expr_node *node) {
+        const Table *t = nullptr;
+        QEH_TRY(subquery(x.index, &t));
+        Col probe;
+        QEH_TRY(eval_plain(rw->table, child, &probe));
+        qeh_column setc{};
+        if (t->cols.size() == 1) {
+            setc = t->cols[0].c;
+        } else if (t->cols.empty() && t->fields.size() <= 1 && t->batches == 0) {
+            setc.dtype = probe.c.dtype;
+        } else {
+            return fail(QEH_E_INVALID, "IN subquery must return exactly one column");
+        }
+        qeh_column res{};
+        QEH_TRY(in_set(ctx_, probe.c, setc, x.op, &res));
+        rw->table.cols.push_back(own(ctx_, res));
+        rw->table.fields.push_back({"", QEH_DT_BOOL, true});
+        *node = qeh_expr_node{};
+        node->kind = QEH_EX_COLUMN;
+        node->index = (int32_t)rw->table.cols.size() - 1;
+        return QEH_OK;
+    }
+
+    // Replace the subquery nodes of `e` (over `in`) by COLUMN / LITERAL nodes, like
+    // rewrite_utf8_compares: temporaries are appended to the operator's inputs (rw->table), so the
+    // original column indices stay valid.
+    int rewrite_subqueries(const Table &in, const qeh_expr &e, SubqRewrite *rw) {
+        rw->table = in;
+        rw->nodes.clear();
+        std::vector<int> start;  // start[i]: first node of the subtree whose root is output node i
+        for (int i = 0; i < e.n_nodes; ++i) {
+            const qeh_expr_node &x = e.nodes[i];
+            const int m = (int)rw->nodes.size();
+            qeh_expr_node node = x;
+            int first = m;
+            switch (x.kind) {
+                case QEH_EX_BINARY:
+                    if (m < 2 || start[m - 1] < 1) return fail(QEH_E_INVALID, "malformed expression (binary)");
+                    first = start[start[m - 1] - 1];
+                    break;
+                case QEH_EX_UNARY:
+                    if (m < 1) return fail(QEH_E_INVALID, "malformed expression (unary)");
+                    first = start[m - 1];
+                    break;
+                case QEH_EX_EXISTS: {
+                    const Table *t = nullptr;
+                    QEH_TRY(subquery(x.index, &t));
+                    node = qeh_expr_node{};
+                    node.kind = QEH_EX_LITERAL;
+                    node.lit_dtype = QEH_DT_BOOL;
+                    node.lit_i64 = ((t->rows > 0) != (x.op != 0)) ? 1 : 0;
+                    break;
+                }
+                case QEH_EX_SCALAR_SUBQUERY: QEH_TRY(scalar_subquery(x, rw, &node)); break;
+                case QEH_EX_IN_SUBQUERY: {
+                    if (m < 1) return fail(QEH_E_INVALID, "malformed expression (IN subquery without a tested expression)");
+                    first = start[m - 1];
+                    const qeh_expr child{rw->nodes.data() + first, m - first};
+                    QEH_TRY(in_subquery(x, child, rw, &node));
+                    rw->nodes.resize(first);
+                    start.resize(first);
+                    break;
+                }
+                default: break;
+            }
+            rw->nodes.push_back(node);
+            start.push_back(first);
+        }
+        rw->expr.nodes = rw->nodes.data();
+        rw->expr.n_nodes = (int32_t)rw->nodes.size();
+        return QEH_OK;
+    }
 
     static std::vector<qeh_column> raw(const Table &t) {
         std::vector<qeh_column> v;
@@ -560,6 +852,15 @@ class Executor {
     }
 
     int eval(const Table &t, const qeh_expr &e, Col *out) {
+        if (has_subquery(e)) {
+            SubqRewrite rw;
+            QEH_TRY(rewrite_subqueries(t, e, &rw));
+            return eval_plain(rw.table, rw.expr, out);
+        }
+        return eval_plain(t, e, out);
+    }
+
+    int eval_plain(const Table &t, const qeh_expr &e, Col *out) {
         const int ci = expr_as_column(&e);
         if (ci >= 0) {
             if (ci >= (int)t.cols.size())
@@ -588,6 +889,11 @@ class Executor {
 
     // Filter keeping only columns `idx` of `in` (in that order) and at most `cap` rows (< 0: all).
     int filter_columns(const Table &in, const qeh_expr &pred, const std::vector<int32_t> &idx, int64_t cap, Table *out) {
+        if (has_subquery(pred)) {  // the temporaries follow the inputs: `idx` is unchanged
+            SubqRewrite rw;
+            QEH_TRY(rewrite_subqueries(in, pred, &rw));
+            return filter_columns(rw.table, rw.expr, idx, cap, out);
+        }
         out->fields.clear();
         out->cols.clear();
         for (int32_t i : idx) out->fields.push_back(in.fields[i]);
@@ -1114,6 +1420,9 @@ class Executor {
                 pred = &child.predicate;
             }
             if (jn && !(jn->join_type == QEH_JOIN_INNER && jn->has_predicate)) jn = nullptr;
+            // a subquery in the predicate: its temporaries would sit between the two sides' columns;
+            // the filter below takes it over the joined table
+            if (jn && pred && has_subquery(*pred)) jn = nullptr;
         }
         if (jn) {
             Table l, r;
@@ -1172,11 +1481,16 @@ class Executor {
         }
         // fused HashAggregate(Filter(X)) for GROUP BY
         if (grouped && child.kind == QEH_PLAN_FILTER && !std::getenv("QEH_NO_FUSION")) {
-            Table in;
-            QEH_TRY(run(child.input, &in, depth + 2));
+            Table in0;
+            QEH_TRY(run(child.input, &in0, depth + 2));
+            SubqRewrite rw;  // subquery temporaries follow the inputs: key and aggregate indices hold
+            const bool subq = has_subquery(child.predicate);
+            if (subq) QEH_TRY(rewrite_subqueries(in0, child.predicate, &rw));
+            const Table &in = subq ? rw.table : in0;
+            const qeh_expr &fpred = subq ? rw.expr : child.predicate;
             const int n = (int)in.cols.size();
-            if (n <= 11 && all_columns(nd.exprs, nd.n_exprs, 0, n) && all_columns(aexprs.data(), nd.n_aggs, 0, n) &&
-                in.batches > 0) {
+            if (n <= 11 && all_columns(nd.exprs, nd.n_exprs, 0, (int)in0.cols.size()) &&
+                all_columns(aexprs.data(), nd.n_aggs, 0, (int)in0.cols.size()) && in.batches > 0) {
                 auto cols = raw(in);
                 std::vector<qeh_column> keys;
                 for (int i = 0; i < nd.n_exprs; ++i) keys.push_back(cols[expr_as_column(&nd.exprs[i])]);
@@ -1185,7 +1499,7 @@ class Executor {
                 std::vector<qeh_column> ok(keys.size()), oa(qa.size());
                 int64_t g = 0;
                 QEH_TRY(hash_aggregate_filtered(ctx_, keys.data(), (int)keys.size(), cols.data(), n, qa.data(),
-                                                (int)qa.size(), cols.data(), n, &child.predicate, in.batches, ok.data(),
+                                                (int)qa.size(), cols.data(), n, &fpred, in.batches, ok.data(),
                                                 oa.data(), &g));
                 for (int i = 0; i < nd.n_exprs; ++i) {
                     const Field &f = in.fields[expr_as_column(&nd.exprs[i])];
@@ -1201,7 +1515,7 @@ class Executor {
                 return QEH_OK;
             }
             Table f;
-            QEH_TRY(filter_table(in, child.predicate, &f));
+            QEH_TRY(filter_table(in0, child.predicate, &f));
             return aggregate_table(nd, f, out);
         }
         Table in;

@@ -224,6 +224,12 @@ int compile_expr(const qeh_expr *e, const int32_t *dtypes, int n_cols, DevProgra
                 ty.back() = res;
                 break;
             }
+            case QEH_EX_SCALAR_SUBQUERY: case QEH_EX_IN_SUBQUERY: case QEH_EX_EXISTS:
+                // the executor replaces these before typing (executor.hip rewrite_subqueries);
+                // here no plan is in reach to run the subplan
+                return fail(QEH_E_UNSUPPORTED,
+                            "subquery expression outside a plan: qeh_filter / qeh_eval / qeh_expr_type cannot run "
+                            "its subplan; use qeh_execute_plan");
             default:
                 return fail(QEH_E_UNSUPPORTED, "expression node kind not supported on the device");
         }

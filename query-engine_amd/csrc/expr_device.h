@@ -153,6 +153,12 @@ __device__ __forceinline__ void load_rows(const ColRef &c, int64_t row0, int64_t
 template <int R>
 __device__ void run_program(const DevProgram &P, const ColSet &cols, int64_t row0, int64_t stride,
                             int64_t n, ExprRegs<R> &X, uint32_t &err) {
+    // rows of this call that exist: a literal is valid on those only (a program of literals alone,
+    // e.g. what an EXISTS subquery becomes, must not select rows at and past n)
+    uint32_t live = 0;
+#pragma unroll
+    for (int r = 0; r < R; ++r)
+        if (row0 + r * stride < n) live |= 1u << r;
     for (int pc = 0; pc < P.n; ++pc) {
         const DevInstr in = P.ins[pc];
         int64_t a[R], b[R], o[R];
@@ -164,7 +170,7 @@ __device__ void run_program(const DevProgram &P, const ColSet &cols, int64_t row
             case D_LIT:
 #pragma unroll
                 for (int r = 0; r < R; ++r) o[r] = in.imm;
-                vo = in.flag ? 0u : ((1u << R) - 1u);
+                vo = in.flag ? 0u : live;
                 break;
             case D_TOF64:
                 get_slot<R>(X, in.a, a, va);

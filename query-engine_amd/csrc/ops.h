@@ -179,6 +179,9 @@ int encode_utf8_keys(qeh_ctx *ctx, const qeh_column *keys, int n_keys, Utf8Keys 
 // probe row that is NULL or whose string the build side lacks comes out NULL.  Both outputs are owned.
 int utf8_join_encode(qeh_ctx *ctx, const qeh_column &build, const qeh_column &probe, qeh_column *out_build_codes,
                      qeh_column *out_probe_codes, int64_t *out_distinct);
+// `probe [NOT] IN (set)` with SQL three-valued logic (k_semi.hip, qeh_in_set): an owned BOOL column
+// of probe.length rows.  The set becomes a bitmap over its key range or a key-only hash set.
+int in_set(qeh_ctx *ctx, const qeh_column &probe, const qeh_column &set, int negated, qeh_column *out);
 // arrow's display name of a column type, as its error messages print it (k_utf8.hip)
 const char *arrow_type_name(int dt);
 inline bool any_utf8(const qeh_column *cols, int n) {

@@ -21,6 +21,7 @@ STATUS_NAMES = {0: "OK", 1: "INVALID", 2: "OVERFLOW", 3: "DIV0", 4: "OOM", 5: "U
 DT_NULL, DT_BOOL, DT_INT32, DT_INT64, DT_FLOAT32, DT_FLOAT64, DT_UTF8, DT_UINT32 = range(8)
 
 EX_COLUMN, EX_LITERAL, EX_BINARY, EX_UNARY = 1, 2, 3, 4
+EX_SCALAR_SUBQUERY, EX_IN_SUBQUERY, EX_EXISTS = 5, 6, 7
 (OP_ADD, OP_SUB, OP_MUL, OP_DIV, OP_MOD, OP_EQ, OP_NEQ, OP_LT, OP_LTE, OP_GT, OP_GTE,
  OP_AND, OP_OR) = range(13)
 UOP_NOT, UOP_MINUS = 0, 1
@@ -112,6 +113,7 @@ SIGNATURES = {
     "qeh_join_filter_aggregate_prelaunch_stats": (I, [P, COLP, I, I, EXPRP, AGGP, I, P, I, I]),
     "qeh_utf8_dict_encode": (I, [P, COLP, COLP, COLP]),
     "qeh_utf8_join_encode": (I, [P, COLP, COLP, COLP, COLP, C.POINTER(I64)]),
+    "qeh_in_set": (I, [P, COLP, COLP, I, COLP]),
     "qeh_sort_indices": (I, [P, COLP, I, C.POINTER(C.c_int8), COLP]),
     "qeh_sort_indices_limit": (I, [P, COLP, I, C.POINTER(C.c_int8), C.c_int64, COLP]),
     "qeh_sort_indices_nulls":(I, [P, COLP, I, C.POINTER(C.c_int8), C.POINTER(C.c_int8), COLP]),

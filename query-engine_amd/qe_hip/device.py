@@ -641,6 +641,12 @@ class Context:
                                                 C.byref(d)))
         return self._wrap(bc), self._wrap(pc), d.value
 
+    def in_set(self, probe: DeviceColumn, set: DeviceColumn, negated: bool = False) -> DeviceColumn:
+        """qeh_in_set: `probe [NOT] IN (set)` as a nullable BOOL column (SQL three-valued logic)."""
+        out = abi.QehColumn()
+        abi.check(self.lib.qeh_in_set(self.h, C.byref(probe.c), C.byref(set.c), 1 if negated else 0, C.byref(out)))
+        return self._wrap(out)
+
     def sort_indices(self, keys: Sequence[DeviceColumn], ascending: Sequence[bool]) -> DeviceColumn:
         ck = self._cols(keys)
         asc = (C.c_int8 * max(len(keys), 1))(*[1 if a else 0 for a in ascending])

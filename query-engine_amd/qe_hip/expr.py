@@ -67,9 +67,16 @@ class PhysicalExpr:
     def columns(self) -> List[int]:
         return sorted({n.index for n in self.postfix() if n.kind == abi.EX_COLUMN})
 
-    def to_c(self):
-        """(QehExpr, keepalive) for a C call."""
+    def to_c(self, subplan=None):
+        """(QehExpr, keepalive) for a C call.  `subplan`: a callable mapping a subquery
+        expression's PhysicalPlan to its root's index in the flattened plan (the plan flattener
+        passes one); without it a subquery expression cannot be encoded -- no plan is in reach."""
         nodes = self.postfix()
+        for n in nodes:
+            if hasattr(n, "_subplan"):
+                if subplan is None:
+                    raise ValueError("subquery expressions are only valid inside a plan run by QueryExecutor")
+                n.index = subplan(n._subplan)
         arr = (abi.QehExprNode * len(nodes))(*nodes)
         e = abi.QehExpr(C.cast(arr, C.POINTER(abi.QehExprNode)), len(nodes))
         # Utf8 literal bytes are referenced by address (index = length, lit_i64 = pointer)
@@ -131,6 +138,44 @@ class UnaryExpr(PhysicalExpr):
     def _emit(self, out):
         self.expr._emit(out)
         out.append(abi.QehExprNode(kind=abi.EX_UNARY, op=self.op))
+
+
+def _subquery_node(kind: int, plan, negated: bool) -> abi.QehExprNode:
+    n = abi.QehExprNode(kind=kind, op=1 if negated else 0, index=-1)
+    n._subplan = plan  # resolved to the subplan root's node index when the plan is flattened
+    return n
+
+
+@dataclass
+class ScalarSubquery(PhysicalExpr):
+    """`PhysicalExpr::ScalarSubquery { plan }` (physical_plan.rs:91-94), uncorrelated: the single
+    value of a one-column subplan (no row: NULL; more than one row: an error)."""
+    plan: object
+
+    def _emit(self, out):
+        out.append(_subquery_node(abi.EX_SCALAR_SUBQUERY, self.plan, False))
+
+
+@dataclass
+class InSubquery(PhysicalExpr):
+    """`PhysicalExpr::InSubquery { expr, plan, negated }` (physical_plan.rs:95-99)."""
+    expr: PhysicalExpr
+    plan: object
+    negated: bool = False
+
+    def _emit(self, out):
+        self.expr._emit(out)
+        out.append(_subquery_node(abi.EX_IN_SUBQUERY, self.plan, self.negated))
+
+
+@dataclass
+class Exists(PhysicalExpr):
+    """`PhysicalExpr::Exists { plan, negated }` (physical_plan.rs:100-104)."""
+    plan: object
+    negated: bool = False
+
+    def _emit(self, out):
+        out.append(_subquery_node(abi.EX_EXISTS, self.plan, self.negated))
 
 
 @dataclass

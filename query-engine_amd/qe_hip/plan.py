@@ -223,7 +223,9 @@ class _Flattener:
         self.sources: List[DataSource] = []
 
     def expr(self, e: PhysicalExpr) -> abi.QehExpr:
-        c, arr = e.to_c()
+        # a subquery expression's subplan is flattened into the same node array (its sources into
+        # the same source list) and the expression node's `index` names its root
+        c, arr = e.to_c(self.add)
         self.keep.append(arr)
         return c
 

@@ -26,12 +26,16 @@
   topk       ORDER BY k LIMIT 100 over 1e8 rows (spread Int64, Float64, Int64 in [0, 1024)): the radix-select
              path of qeh_sort_indices_limit against the full sort in the same process, then the limit / n, n and
              candidate-share sweeps behind its fallback constants
+  semi       k IN (set) through qeh_in_set: 1e9 Int64 probe keys against a dense 1e7-key set (bitmap form) and
+             1e8 probe keys against 1e7 sparse 64-bit keys (hash-set form); beside each the byte floor (8 B
+             read + 1 bit written per row at 8 TB/s) and the closest operator there was before,
+             hash_join_inner of the same probe against the same (distinct) set emitting the probe key only
   cfg4leg    config 4's per-rank device leg at N = 8 (fused filter + 8-way exchange pass over 1e9
              rows, the dim shard's exchange pass, the local join of what the rank receives)
 
 Prints one JSON line per config: rows/s, ms per run, algorithmic GB/s and
 fraction of 8 TB/s, and the oracle's rows/s on a bounded sample (1 thread).
-usage: python tools/bench_configs.py [--only cfg2,cfg3,cfg5,window,filter,limit,plan,left,full,merge,encode,partition,utf8_groupby,utf8_sort,utf8_join,topk] [--scale 1.0]
+usage: python tools/bench_configs.py [--only cfg2,cfg3,cfg5,window,filter,limit,plan,left,full,merge,encode,partition,utf8_groupby,utf8_sort,utf8_join,topk,semi] [--scale 1.0]
 """
 import argparse
 import json
@@ -911,6 +915,41 @@ def cfg_topk(ctx, scale):
             del key
 
 
+def cfg_semi(ctx, scale):
+    """k IN (set) as a nullable BOOL column (qeh_in_set, csrc/k_semi.hip), both set forms.  Every probe key
+    lies inside the set's range, so every row pays its lookup (none is answered by the range check)."""
+    nd = 10_000_000
+    shapes = [("bitmap", int(1e9 * scale),
+               lambda n: ctx.generate(abi.GEN_UNIFORM_MOD, SEED, 2, n, nd),
+               lambda: ctx.generate(abi.GEN_PERMUTATION, SEED, 0, nd, nd), "dense set: a permutation of [0, 1e7)"),
+              ("hash", int(1e8 * scale),
+               lambda n: ctx.generate(abi.GEN_SPARSE_KEY, SEED, 2, n, nd),
+               lambda: ctx.generate(abi.GEN_SPARSE_KEY, SEED, 2, nd, 0), "sparse set: 1e7 distinct 64-bit keys")]
+    for form, n, gen_probe, gen_set, what in shapes:
+        probe, sset = gen_probe(n), gen_set()
+
+        def semi():
+            out = ctx.in_set(probe, sset)
+            out.release()
+        wall, kt, _ = timed(ctx, semi, 5, ["semi_probe_bitmap", "semi_probe_hash", "semi_build_bitmap", "semi_build_hash"])
+        taken = "bitmap" if kt["semi_probe_bitmap"] > 0 else "hash"
+
+        def join():  # what the parent could do: the pairs of an inner join, probe key only (the set is distinct)
+            p, b, rows = ctx.hash_join_inner(probe, [probe], sset, [])
+            for c in p + b:
+                c.release()
+            return rows
+        jwall, jkt, jrows = timed(ctx, join, 3, ["join_probe", "join_gather", "join_build"])
+        probe_ms = kt["semi_probe_" + taken]
+        alg = (8.0 + 1.0 / 8.0) * n
+        line(f"semi k IN (set), {n} probes x {nd} keys, {form} form", n, wall, alg, probe_ms, "k_semi_probe", None,
+             {"set": what, "form_taken": taken, "build_ms": kt["semi_build_" + taken],
+              "byte_floor_ms": alg / (PEAK * 1e9) * 1e3, "probe_over_floor": probe_ms / (alg / (PEAK * 1e9) * 1e3),
+              "hash_join_inner_probe_key_only_ms": jwall * 1e3, "hash_join_inner_kernels_ms": jkt,
+              "hash_join_inner_rows": jrows, "speedup_vs_hash_join_inner_wall": jwall / wall})
+        del probe, sset
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--only", default="cfg2,cfg3,cfg5,filter")
@@ -927,7 +966,7 @@ def main():
          "merge": cfg_merge, "encode": cfg_encode, "shapes": cfg_metric_shapes, "partition": cfg_partition, "cfg3w": cfg3_wide, "window": cfg_window,
          "cfg4leg": cfg4_leg, "cfg4items": cfg4_items_leg, "cfg5leg": cfg5_leg,
          "window_lsd": cfg_window_lsd, "utf8_groupby": cfg_utf8_groupby, "utf8_sort": cfg_utf8_sort, "utf8_join": cfg_utf8_join,
-         "topk": cfg_topk}[name](ctx, args.scale)
+         "topk": cfg_topk, "semi": cfg_semi}[name](ctx, args.scale)
         ctx.sync()
         abi.check(ctx.lib.qeh_pool_trim(ctx.h))
     ctx.close()
