@@ -79,8 +79,8 @@ typedef struct qeh_column {
 /* ---- expressions: postfix encoding of PhysicalExpr ------------------------
  * physical_plan.rs:74-142.  Only the variants the converters emit
  * (crates/query-pgwire/src/backend.rs:727-756) are representable:
- * Column{index}, Literal(ScalarValue), BinaryExpr, UnaryExpr -- and, inside a
- * plan only, the planner's ScalarSubquery / InSubquery / Exists.  Children come
+ * Column{index}, Literal(ScalarValue), BinaryExpr, UnaryExpr, ScalarFunction -- and,
+ * inside a plan only, the planner's ScalarSubquery / InSubquery / Exists.  Children come
  * before parents (post-order); the last node is the root.  Type coercion is
  * NOT encoded: the library applies the reference's rules
  * (operators.rs:616-709) itself.                                             */
@@ -99,7 +99,39 @@ enum qeh_expr_kind {
      * QEH_E_UNSUPPORTED. */
     QEH_EX_SCALAR_SUBQUERY = 5, /* one column; 0 rows -> NULL, 1 row -> its value, more -> QEH_E_INVALID */
     QEH_EX_IN_SUBQUERY = 6,     /* child [NOT] IN (one-column subplan): qeh_in_set's rules            */
-    QEH_EX_EXISTS = 7           /* the subplan returns at least one row, flipped by `op`              */
+    QEH_EX_EXISTS = 7,          /* the subplan returns at least one row, flipped by `op`              */
+    /* PhysicalExpr::ScalarFunction { func, args } (physical_plan.rs:112-116), evaluated as
+     * evaluate_scalar_function does (operators.rs:64-259): `op` = enum qeh_scalar_func, `index` =
+     * n_args; the node is the postfix parent of the n_args argument subexpressions that precede it,
+     * in argument order.  Every argument is evaluated first (its own error wins), then the arity is
+     * checked (QEH_E_INVALID, "UPPER requires 1 argument"), then the argument types (QEH_E_TYPE,
+     * "CEIL requires float argument"); arguments past the ones a function reads are evaluated and
+     * ignored.  Needs no plan: valid in qeh_eval / qeh_filter / qeh_filter_limit / qeh_expr_type
+     * and anywhere in a plan; the fused entry points (qeh_filter_aggregate,
+     * qeh_join_filter_aggregate*, qeh_filter_partition_hash_move, qeh_fused_items_*) return
+     * QEH_E_UNSUPPORTED for it. */
+    QEH_EX_SCALAR_FUNCTION = 8
+};
+/* Same order as `ScalarFunctionType` (physical_plan.rs:183-205).
+ *   UPPER / LOWER (Utf8 -> Utf8): ASCII letters only; a byte >= 0x80 in a non-NULL row is
+ *     QEH_E_UNSUPPORTED (Rust's to_uppercase / to_lowercase are full Unicode: fall back).  NULL rows
+ *     come back NULL with empty slots.
+ *   LENGTH (Utf8 -> Int64): byte lengths.
+ *   CONCAT (Utf8... -> Utf8): row i = every argument's slot i (the bytes between its offsets,
+ *     whatever its validity: the reference reads value(i)); no NULLs; Utf8 literals broadcast;
+ *     more than 2^31-1 result bytes is QEH_E_UNSUPPORTED.
+ *   ABS (Float64 -> Float64, Int64 -> Int64, wrapping at INT64_MIN); CEIL / FLOOR / ROUND (half
+ *     away from zero) / SQRT (Float64 -> Float64, bit-exact); POWER (Float64, Float64 -> Float64).
+ *     Any other argument type, Int32 / Float32 and an Int64 literal exponent included, is the
+ *     reference's type error.  NULL exactly where an argument they read is NULL.
+ *   COALESCE: its first argument, unchanged (operators.rs:249-250).
+ *   SUBSTRING / TRIM / REPLACE / NULLIF: QEH_E_UNSUPPORTED with the reference's "... function not
+ *     yet fully implemented"; TO_TSVECTOR / TO_TSQUERY: QEH_E_UNSUPPORTED (Unicode tokenising). */
+enum qeh_scalar_func {
+    QEH_FN_UPPER = 0, QEH_FN_LOWER = 1, QEH_FN_LENGTH = 2, QEH_FN_CONCAT = 3, QEH_FN_SUBSTRING = 4,
+    QEH_FN_TRIM = 5, QEH_FN_REPLACE = 6, QEH_FN_ABS = 7, QEH_FN_CEIL = 8, QEH_FN_FLOOR = 9,
+    QEH_FN_ROUND = 10, QEH_FN_SQRT = 11, QEH_FN_POWER = 12, QEH_FN_COALESCE = 13, QEH_FN_NULLIF = 14,
+    QEH_FN_TO_TSVECTOR = 15, QEH_FN_TO_TSQUERY = 16
 };
 /* Same order as `BinaryOp` (physical_plan.rs:119-136; TsMatch excluded). */
 enum qeh_binop {
@@ -112,17 +144,20 @@ enum qeh_unop { QEH_UOP_NOT = 0, QEH_UOP_MINUS = 1 };
 
 typedef struct qeh_expr_node {
     int32_t kind;        /* enum qeh_expr_kind                              */
-    int32_t op;          /* qeh_binop / qeh_unop; subquery kinds: negated   */
+    int32_t op;          /* qeh_binop / qeh_unop; subquery kinds: negated;
+                            SCALAR_FUNCTION: qeh_scalar_func                */
     int32_t index;       /* COLUMN: input column index; UTF8 LITERAL: byte length;
-                            subquery kinds: the subplan's root node          */
+                            subquery kinds: the subplan's root node;
+                            SCALAR_FUNCTION: n_args                          */
     int32_t lit_dtype;   /* LITERAL: enum qeh_dtype (NULL = ScalarValue::Null) */
     int32_t lit_is_null; /* LITERAL: typed None (e.g. Int64(None))         */
     int32_t _pad;
     int64_t lit_i64;     /* BOOL/INT32/INT64 literal; UTF8 LITERAL: host address of
                             its bytes (read during the call only).  Utf8 operands
-                            appear only in comparisons of two leaves (column /
-                            literal), evaluated by byte-wise lexicographic order,
-                            operators.rs:509-538 on StringArray             */
+                            appear in comparisons of two leaves (column / literal /
+                            a function's Utf8 result), evaluated by byte-wise
+                            lexicographic order, operators.rs:509-538 on
+                            StringArray, and as scalar function arguments   */
     double lit_f64;      /* FLOAT32/FLOAT64 literal                         */
 } qeh_expr_node;
 

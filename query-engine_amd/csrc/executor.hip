@@ -73,6 +73,30 @@ inline bool has_subquery(const qeh_expr &e) {
     return false;
 }
 
+// Scalar functions (QEH_EX_SCALAR_FUNCTION) need no rewrite here: qeh_eval and qeh_filter_limit
+// materialise them (rewrite_scalar_functions), and every expression of a plan goes through eval /
+// filter_columns.  The fused kernels interpret an expression program that has no function op, so the
+// fusion decisions decline a predicate that holds one and the unfused chain runs instead.
+inline bool has_function(const qeh_expr &e) { return expr_has_function(&e); }
+
+// start[i] for postfix node i given the starts of the nodes before it: the first node of the
+// subtree whose root is node i (-1: malformed).
+inline int subtree_start(const qeh_expr_node &x, int i, const std::vector<int> &start) {
+    int n_children = 0;
+    switch (x.kind) {
+        case QEH_EX_BINARY: n_children = 2; break;
+        case QEH_EX_UNARY: case QEH_EX_IN_SUBQUERY: n_children = 1; break;
+        case QEH_EX_SCALAR_FUNCTION: n_children = std::max(x.index, 0); break;
+        default: break;
+    }
+    int first = i;
+    for (int c = 0; c < n_children; ++c) {
+        if (first < 1) return -1;
+        first = start[first - 1];
+    }
+    return first;
+}
+
 // An expression with its subquery nodes replaced (rewrite_subqueries): `table` = the operator's
 // input with the temporary columns appended, `expr` reads it.  Owns the host bytes of Utf8 scalars.
 struct SubqRewrite {
@@ -816,6 +840,10 @@ class Executor {
                     if (m < 1) return fail(QEH_E_INVALID, "malformed expression (unary)");
                     first = start[m - 1];
                     break;
+                case QEH_EX_SCALAR_FUNCTION:  // stays; qeh_eval / qeh_filter_limit materialise it
+                    first = subtree_start(x, m, start);
+                    if (first < 0) return fail(QEH_E_INVALID, "malformed expression (scalar function arguments)");
+                    break;
                 case QEH_EX_EXISTS: {
                     const Table *t = nullptr;
                     QEH_TRY(subquery(x.index, &t));
@@ -871,6 +899,13 @@ class Executor {
         auto cols = raw(t);
         qeh_column r{};
         QEH_TRY(qeh_eval(ctx_, cols.data(), (int)cols.size(), &e, t.rows, &r));
+        if (!r.owned) {  // COALESCE(column, ..): a view of an input, which keeps its owner
+            const int ai = expr_aliased_column(&e);
+            if (ai < 0 || ai >= (int)t.cols.size() || t.cols[ai].c.values != r.values)
+                return fail(QEH_E_INTERNAL, "eval returned a view of a column that is not an input");
+            *out = t.cols[ai];
+            return QEH_OK;
+        }
         *out = own(ctx_, r);
         return QEH_OK;
     }
@@ -1097,6 +1132,9 @@ class Executor {
             } else if (x.kind == QEH_EX_UNARY) {
                 ok = i >= 1;
                 if (ok) start[i] = start[i - 1];
+            } else if (x.kind == QEH_EX_SCALAR_FUNCTION) {
+                start[i] = subtree_start(x, i, start);
+                ok = start[i] >= 0;
             } else {
                 start[i] = i;
             }
@@ -1423,6 +1461,8 @@ class Executor {
             // a subquery in the predicate: its temporaries would sit between the two sides' columns;
             // the filter below takes it over the joined table
             if (jn && pred && has_subquery(*pred)) jn = nullptr;
+            // a scalar function: the fused kernel's expression program cannot evaluate it
+            if (jn && pred && has_function(*pred)) jn = nullptr;
         }
         if (jn) {
             Table l, r;
@@ -1489,7 +1529,8 @@ class Executor {
             const Table &in = subq ? rw.table : in0;
             const qeh_expr &fpred = subq ? rw.expr : child.predicate;
             const int n = (int)in.cols.size();
-            if (n <= 11 && all_columns(nd.exprs, nd.n_exprs, 0, (int)in0.cols.size()) &&
+            // (a scalar function in the predicate: the unfused filter below materialises it)
+            if (n <= 11 && !has_function(child.predicate) && all_columns(nd.exprs, nd.n_exprs, 0, (int)in0.cols.size()) &&
                 all_columns(aexprs.data(), nd.n_aggs, 0, (int)in0.cols.size()) && in.batches > 0) {
                 auto cols = raw(in);
                 std::vector<qeh_column> keys;

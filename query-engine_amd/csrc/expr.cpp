@@ -71,6 +71,33 @@ int expr_as_column(const qeh_expr *e) {
     return -1;
 }
 
+int expr_aliased_column(const qeh_expr *e) {
+    if (!e || !e->nodes || e->n_nodes <= 0) return -1;
+    std::vector<int> start(e->n_nodes);  // start[i]: first node of the subtree whose root is node i
+    for (int i = 0; i < e->n_nodes; ++i) {
+        const qeh_expr_node &nd = e->nodes[i];
+        int n_children = 0;
+        if (nd.kind == QEH_EX_BINARY) n_children = 2;
+        else if (nd.kind == QEH_EX_UNARY || nd.kind == QEH_EX_IN_SUBQUERY) n_children = 1;
+        else if (nd.kind == QEH_EX_SCALAR_FUNCTION) n_children = nd.index > 0 ? nd.index : 0;
+        int first = i;
+        for (int c = 0; c < n_children; ++c) {
+            if (first < 1) return -1;
+            first = start[first - 1];
+        }
+        start[i] = first;
+    }
+    int root = e->n_nodes - 1;
+    if (start[root] != 0) return -1;
+    for (;;) {
+        const qeh_expr_node &nd = e->nodes[root];
+        if (nd.kind == QEH_EX_COLUMN) return nd.index;
+        if (nd.kind != QEH_EX_SCALAR_FUNCTION || nd.op != QEH_FN_COALESCE || nd.index < 1) return -1;
+        for (int a = nd.index - 1; a >= 1; --a) root = start[root - 1];  // step over arguments n-1 .. 1
+        root -= 1;
+    }
+}
+
 uint64_t expr_columns(const qeh_expr *e) {
     uint64_t m = 0;
     if (!e) return 0;
@@ -78,6 +105,157 @@ uint64_t expr_columns(const qeh_expr *e) {
         if (e->nodes[i].kind == QEH_EX_COLUMN && e->nodes[i].index >= 0 && e->nodes[i].index < 64)
             m |= 1ull << e->nodes[i].index;
     return m;
+}
+
+// Typing of one unary / binary operator (the rules in the header comment); compile_expr and
+// type_expr share them.  cl / cr: the operand types a comparison is carried out in.
+static int type_unary(int op, int t) {
+    if (op == QEH_UOP_NOT) {
+        if (t != QEH_DT_BOOL) return fail(QEH_E_TYPE, "NOT operator requires boolean array");
+        return QEH_OK;
+    }
+    if (op == QEH_UOP_MINUS) {
+        if (!is_num(t)) return fail(QEH_E_TYPE, "Unsupported type for negation");
+        return QEH_OK;
+    }
+    return fail(QEH_E_INVALID, "unknown unary operator");
+}
+
+static int type_binary(int op, int lt, int rt, int *res, int *cl, int *cr) {
+    *cl = lt;
+    *cr = rt;
+    switch (op) {
+        case QEH_OP_ADD: case QEH_OP_SUB: case QEH_OP_MUL: case QEH_OP_DIV: {
+            static const char *nm[] = {"addition", "subtraction", "multiplication", "division"};
+            if (lt != rt || !is_num(lt)) return fail(QEH_E_TYPE, std::string("Unsupported types for ") + nm[op]);
+            *res = lt;
+            return QEH_OK;
+        }
+        case QEH_OP_MOD:
+            if (lt != rt || !is_int(lt)) return fail(QEH_E_TYPE, "Modulo operation requires integer arrays");
+            *res = lt;
+            return QEH_OK;
+        case QEH_OP_EQ: case QEH_OP_NEQ: case QEH_OP_LT: case QEH_OP_LTE: case QEH_OP_GT: case QEH_OP_GTE:
+            coerce(lt, rt, cl, cr);
+            if (*cl != *cr || *cl == QEH_DT_NULL)
+                return fail(QEH_E_TYPE, std::string("Invalid argument error: Invalid comparison operation: ") +
+                                            dt_name(*cl) + " " + cmp_sym(op) + " " + dt_name(*cr));
+            *res = QEH_DT_BOOL;
+            return QEH_OK;
+        case QEH_OP_AND: case QEH_OP_OR:
+            if (lt != QEH_DT_BOOL || rt != QEH_DT_BOOL)
+                return fail(QEH_E_TYPE, op == QEH_OP_AND ? "AND requires boolean arrays" : "OR requires boolean arrays");
+            *res = QEH_DT_BOOL;
+            return QEH_OK;
+        default: return fail(QEH_E_UNSUPPORTED, "binary operator not supported on the device");
+    }
+}
+
+static const char *kSubqueryOutsidePlan =
+    "subquery expression outside a plan: qeh_filter / qeh_eval / qeh_expr_type cannot run "
+    "its subplan; use qeh_execute_plan";
+
+const char *scalar_fn_name(int func) {
+    static const char *nm[] = {"UPPER", "LOWER", "LENGTH", "CONCAT", "SUBSTRING", "TRIM", "REPLACE", "ABS", "CEIL",
+                               "FLOOR", "ROUND", "SQRT", "POWER", "COALESCE", "NULLIF", "TO_TSVECTOR", "TO_TSQUERY"};
+    return func >= 0 && func <= QEH_FN_TO_TSQUERY ? nm[func] : "?";
+}
+
+bool expr_has_function(const qeh_expr *e) {
+    for (int i = 0; e && e->nodes && i < e->n_nodes; ++i)
+        if (e->nodes[i].kind == QEH_EX_SCALAR_FUNCTION) return true;
+    return false;
+}
+
+// evaluate_scalar_function's checks after the arguments are evaluated (operators.rs:74-259):
+// arity first, then the types of the arguments the function reads.
+int scalar_fn_type(int func, const int *at, int n_args, int *out_type) {
+    const std::string name = scalar_fn_name(func);
+    switch (func) {
+        case QEH_FN_UPPER: case QEH_FN_LOWER: case QEH_FN_LENGTH:
+            if (n_args < 1) return fail(QEH_E_INVALID, name + " requires 1 argument");
+            if (at[0] != QEH_DT_UTF8) return fail(QEH_E_TYPE, name + " requires string argument");
+            *out_type = func == QEH_FN_LENGTH ? QEH_DT_INT64 : QEH_DT_UTF8;
+            return QEH_OK;
+        case QEH_FN_CONCAT:
+            if (n_args < 1) return fail(QEH_E_INVALID, "CONCAT requires at least 1 argument");
+            for (int i = 0; i < n_args; ++i)
+                if (at[i] != QEH_DT_UTF8) return fail(QEH_E_TYPE, "CONCAT requires string arguments");
+            *out_type = QEH_DT_UTF8;
+            return QEH_OK;
+        case QEH_FN_ABS:
+            if (n_args < 1) return fail(QEH_E_INVALID, "ABS requires 1 argument");
+            if (at[0] != QEH_DT_FLOAT64 && at[0] != QEH_DT_INT64) return fail(QEH_E_TYPE, "ABS requires numeric argument");
+            *out_type = at[0];
+            return QEH_OK;
+        case QEH_FN_CEIL: case QEH_FN_FLOOR: case QEH_FN_ROUND: case QEH_FN_SQRT:
+            if (n_args < 1) return fail(QEH_E_INVALID, name + " requires 1 argument");
+            if (at[0] != QEH_DT_FLOAT64) return fail(QEH_E_TYPE, name + " requires float argument");
+            *out_type = QEH_DT_FLOAT64;
+            return QEH_OK;
+        case QEH_FN_POWER:
+            if (n_args < 2) return fail(QEH_E_INVALID, "POWER requires 2 arguments");
+            if (at[0] != QEH_DT_FLOAT64 || at[1] != QEH_DT_FLOAT64) return fail(QEH_E_TYPE, "POWER requires float arguments");
+            *out_type = QEH_DT_FLOAT64;
+            return QEH_OK;
+        case QEH_FN_COALESCE:
+            if (n_args < 1) return fail(QEH_E_INVALID, "COALESCE requires at least 1 argument");
+            *out_type = at[0];
+            return QEH_OK;
+        case QEH_FN_SUBSTRING: case QEH_FN_TRIM: case QEH_FN_REPLACE: case QEH_FN_NULLIF: {
+            // format!("{:?} function not yet fully implemented", func)
+            static const char *dbg[] = {"Substring", "Trim", "Replace", "Nullif"};
+            const int k = func == QEH_FN_NULLIF ? 3 : func - QEH_FN_SUBSTRING;
+            return fail(QEH_E_UNSUPPORTED, std::string(dbg[k]) + " function not yet fully implemented");
+        }
+        case QEH_FN_TO_TSVECTOR: case QEH_FN_TO_TSQUERY:
+            return fail(QEH_E_UNSUPPORTED, name + " is not evaluated on the device (Unicode tokenising)");
+        default: return fail(QEH_E_INVALID, "unknown scalar function " + std::to_string(func));
+    }
+}
+
+// The reference's typing of `e` alone: Utf8 leaves and scalar functions included, no device program.
+int type_expr(const qeh_expr *e, const int32_t *dtypes, int n_cols, int32_t *out_type) {
+    if (!e || e->n_nodes <= 0 || !e->nodes) return fail(QEH_E_INVALID, "empty expression");
+    std::vector<int> ty;
+    for (int i = 0; i < e->n_nodes; ++i) {
+        const qeh_expr_node &nd = e->nodes[i];
+        switch (nd.kind) {
+            case QEH_EX_COLUMN:
+                if (nd.index < 0 || nd.index >= n_cols)
+                    return fail(QEH_E_INVALID, "Column index " + std::to_string(nd.index) + " out of bounds");
+                ty.push_back(dtypes[nd.index]);
+                break;
+            case QEH_EX_LITERAL: ty.push_back(nd.lit_is_null ? QEH_DT_NULL : nd.lit_dtype); break;
+            case QEH_EX_UNARY:
+                if (ty.empty()) return fail(QEH_E_INVALID, "malformed expression (unary)");
+                QEH_TRY(type_unary(nd.op, ty.back()));
+                break;
+            case QEH_EX_BINARY: {
+                if (ty.size() < 2) return fail(QEH_E_INVALID, "malformed expression (binary)");
+                int res, cl, cr;
+                QEH_TRY(type_binary(nd.op, ty[ty.size() - 2], ty.back(), &res, &cl, &cr));
+                ty.pop_back();
+                ty.back() = res;
+                break;
+            }
+            case QEH_EX_SCALAR_FUNCTION: {
+                if (nd.index < 0 || (size_t)nd.index > ty.size())
+                    return fail(QEH_E_INVALID, "malformed expression (scalar function arguments)");
+                int res;
+                QEH_TRY(scalar_fn_type(nd.op, ty.data() + (ty.size() - nd.index), nd.index, &res));
+                ty.resize(ty.size() - nd.index);
+                ty.push_back(res);
+                break;
+            }
+            case QEH_EX_SCALAR_SUBQUERY: case QEH_EX_IN_SUBQUERY: case QEH_EX_EXISTS:
+                return fail(QEH_E_UNSUPPORTED, kSubqueryOutsidePlan);
+            default: return fail(QEH_E_UNSUPPORTED, "expression node kind not supported on the device");
+        }
+    }
+    if (ty.size() != 1) return fail(QEH_E_INVALID, "malformed expression (stack)");
+    *out_type = ty[0];
+    return QEH_OK;
 }
 
 int compile_expr(const qeh_expr *e, const int32_t *dtypes, int n_cols, DevProgram *out) {
@@ -139,16 +317,8 @@ int compile_expr(const qeh_expr *e, const int32_t *dtypes, int n_cols, DevProgra
                 if (ty.empty()) return fail(QEH_E_INVALID, "malformed expression (unary)");
                 int t = ty.back();
                 int d = (int)ty.size() - 1;
-                if (nd.op == QEH_UOP_NOT) {
-                    if (t != QEH_DT_BOOL)
-                        return fail(QEH_E_TYPE, "NOT operator requires boolean array");
-                    in.op = D_NOT;
-                } else if (nd.op == QEH_UOP_MINUS) {
-                    if (!is_num(t)) return fail(QEH_E_TYPE, "Unsupported type for negation");
-                    in.op = D_NEG;
-                } else {
-                    return fail(QEH_E_INVALID, "unknown unary operator");
-                }
+                QEH_TRY(type_unary(nd.op, t));
+                in.op = nd.op == QEH_UOP_NOT ? D_NOT : D_NEG;
                 in.t = (uint8_t)t;
                 in.dst = (uint8_t)d;
                 in.a = (uint8_t)d;
@@ -163,32 +333,22 @@ int compile_expr(const qeh_expr *e, const int32_t *dtypes, int n_cols, DevProgra
                 in.dst = (uint8_t)dl;
                 in.a = (uint8_t)dl;
                 in.b = (uint8_t)dr;
-                int res;
+                int res, cl, cr;
+                QEH_TRY(type_binary(nd.op, lt, rt, &res, &cl, &cr));
                 switch (nd.op) {
-                    case QEH_OP_ADD: case QEH_OP_SUB: case QEH_OP_MUL: case QEH_OP_DIV: {
-                        static const char *nm[] = {"addition", "subtraction", "multiplication", "division"};
-                        if (lt != rt || !is_num(lt))
-                            return fail(QEH_E_TYPE, std::string("Unsupported types for ") + nm[nd.op]);
+                    case QEH_OP_ADD: case QEH_OP_SUB: case QEH_OP_MUL: case QEH_OP_DIV:
                         in.op = (uint8_t)(D_ADD + nd.op);
                         in.t = (uint8_t)lt;
-                        res = lt;
                         break;
-                    }
-                    case QEH_OP_MOD: {
-                        if (lt != rt || !is_int(lt))
-                            return fail(QEH_E_TYPE, "Modulo operation requires integer arrays");
+                    case QEH_OP_MOD:
                         in.op = D_MOD;
                         in.t = (uint8_t)lt;
-                        res = lt;
                         break;
-                    }
-                    case QEH_OP_EQ: case QEH_OP_NEQ: case QEH_OP_LT: case QEH_OP_LTE:
-                    case QEH_OP_GT: case QEH_OP_GTE: {
-                        int cl, cr;
-                        coerce(lt, rt, &cl, &cr);
-                        if (cl != cr || cl == QEH_DT_NULL)
-                            return fail(QEH_E_TYPE, std::string("Invalid argument error: Invalid comparison operation: ") +
-                                                        dt_name(cl) + " " + cmp_sym(nd.op) + " " + dt_name(cr));
+                    case QEH_OP_AND: case QEH_OP_OR:
+                        in.op = nd.op == QEH_OP_AND ? D_AND : D_OR;
+                        in.t = QEH_DT_BOOL;
+                        break;
+                    default: {  // comparisons
                         if (cl == QEH_DT_FLOAT64 && lt != QEH_DT_FLOAT64 && lt != QEH_DT_FLOAT32) {
                             DevInstr c{};
                             c.op = D_TOF64; c.t = (uint8_t)lt; c.dst = (uint8_t)dl; c.a = (uint8_t)dl;
@@ -202,22 +362,9 @@ int compile_expr(const qeh_expr *e, const int32_t *dtypes, int n_cols, DevProgra
                         in.op = (uint8_t)(D_EQ + (nd.op - QEH_OP_EQ));
                         // Float32 stays Float32 only when both sides are Float32; slots hold
                         // exact doubles, so compare as Float64 either way.
-                        int ct = cl == QEH_DT_FLOAT32 ? QEH_DT_FLOAT64 : cl;
-                        in.t = (uint8_t)ct;
-                        res = QEH_DT_BOOL;
+                        in.t = (uint8_t)(cl == QEH_DT_FLOAT32 ? QEH_DT_FLOAT64 : cl);
                         break;
                     }
-                    case QEH_OP_AND: case QEH_OP_OR: {
-                        if (lt != QEH_DT_BOOL || rt != QEH_DT_BOOL)
-                            return fail(QEH_E_TYPE, nd.op == QEH_OP_AND ? "AND requires boolean arrays"
-                                                                         : "OR requires boolean arrays");
-                        in.op = nd.op == QEH_OP_AND ? D_AND : D_OR;
-                        in.t = QEH_DT_BOOL;
-                        res = QEH_DT_BOOL;
-                        break;
-                    }
-                    default:
-                        return fail(QEH_E_UNSUPPORTED, "binary operator not supported on the device");
                 }
                 QEH_TRY(emit(in));
                 ty.pop_back();
@@ -227,9 +374,14 @@ int compile_expr(const qeh_expr *e, const int32_t *dtypes, int n_cols, DevProgra
             case QEH_EX_SCALAR_SUBQUERY: case QEH_EX_IN_SUBQUERY: case QEH_EX_EXISTS:
                 // the executor replaces these before typing (executor.hip rewrite_subqueries);
                 // here no plan is in reach to run the subplan
+                return fail(QEH_E_UNSUPPORTED, kSubqueryOutsidePlan);
+            case QEH_EX_SCALAR_FUNCTION:
+                // qeh_eval / qeh_filter and the plan executor materialise functions into columns
+                // first (rewrite_scalar_functions, k_scalar_fn.hip); the device program has no such op
                 return fail(QEH_E_UNSUPPORTED,
-                            "subquery expression outside a plan: qeh_filter / qeh_eval / qeh_expr_type cannot run "
-                            "its subplan; use qeh_execute_plan");
+                            std::string("scalar function expression (QEH_EX_SCALAR_FUNCTION, ") + scalar_fn_name(nd.op) +
+                                ") is not part of a kernel's expression program: evaluate it with qeh_eval / qeh_filter "
+                                "or inside a plan");
             default:
                 return fail(QEH_E_UNSUPPORTED, "expression node kind not supported on the device");
         }
@@ -333,6 +485,13 @@ bool lower_to_terms(const qeh_expr *e, const int32_t *dtypes, int n_cols, PredTe
 
 extern "C" int qeh_expr_type(const int32_t *col_dtypes, int n_cols, const qeh_expr *expr,
                              int32_t *out_dtype) {
+    if (qeh::expr_has_function(expr)) {  // typing alone: Utf8 operands and functions emit no program
+        int32_t t = 0;
+        int s = qeh::type_expr(expr, col_dtypes, n_cols, &t);
+        if (s != QEH_OK) return s;
+        if (out_dtype) *out_dtype = t;
+        return QEH_OK;
+    }
     qeh::DevProgram p;
     int s = qeh::compile_expr(expr, col_dtypes, n_cols, &p);
     if (s != QEH_OK) return s;

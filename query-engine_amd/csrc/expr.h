@@ -61,10 +61,22 @@ constexpr uint32_t kErrSpin = 8u;
 // Compile `e` over columns of `dtypes`.  Returns QEH_OK or an error status with
 // qeh_last_error set to the reference's message.
 int compile_expr(const qeh_expr *e, const int32_t *dtypes, int n_cols, DevProgram *out);
+// The result type of `e` by the reference's typing alone, no device program: Utf8 columns and
+// literals and scalar functions (QEH_EX_SCALAR_FUNCTION) included, which compile_expr refuses.
+int type_expr(const qeh_expr *e, const int32_t *dtypes, int n_cols, int32_t *out_type);
+// One scalar function's arity check, then its argument-type check (operators.rs:74-259), with the
+// reference's messages; *out_type = its result type.
+int scalar_fn_type(int func, const int *arg_types, int n_args, int *out_type);
+const char *scalar_fn_name(int func);
+bool expr_has_function(const qeh_expr *e);
 // Try to lower to the fast term list (only for BOOL-typed predicates).
 bool lower_to_terms(const qeh_expr *e, const int32_t *dtypes, int n_cols, PredTerms *out);
 // Index of the column a bare Column expression refers to, else -1.
 int expr_as_column(const qeh_expr *e);
+// Index of the input column whose buffers qeh_eval returns un-owned (owned = 0) for `e`: a bare
+// Column, or COALESCE chains whose first arguments end in one (COALESCE is its first argument,
+// unchanged).  -1: the result of `e` is a column of its own.
+int expr_aliased_column(const qeh_expr *e);
 // Columns referenced by an expression (bitmask over <= 64 columns).
 uint64_t expr_columns(const qeh_expr *e);
 

@@ -384,7 +384,15 @@ static int filter_impl(qeh_ctx *ctx, const qeh_column *cols, int n_cols, const q
     DeviceGuard dg(ctx->device);
     for (int j = 0; j < n_out; ++j)
         if (out_idx[j] < 0 || out_idx[j] >= n_cols) return fail(QEH_E_INVALID, "filter output column index out of range");
-    // Utf8 comparisons become BOOL columns appended after the inputs (k_utf8.hip)
+    // scalar functions become columns appended after the inputs (k_scalar_fn.hip) ...
+    FnRewrite fw;
+    QEH_TRY(rewrite_scalar_functions(ctx, cols, n_cols, n_cols > 0 ? cols[0].length : 0, predicate, &fw));
+    if (fw.changed) {
+        cols = fw.cols.data();
+        n_cols = (int)fw.cols.size();
+        predicate = &fw.expr;
+    }
+    // ... then Utf8 comparisons become BOOL columns appended after those (k_utf8.hip)
     Utf8Rewrite uw;
     QEH_TRY(rewrite_utf8_compares(ctx, cols, n_cols, predicate, &uw));
     if (uw.changed) {
@@ -578,7 +586,15 @@ extern "C" int qeh_eval(qeh_ctx *ctx, const qeh_column *cols, int n_cols, const 
     DeviceGuard dg(ctx->device);
     for (int i = 0; i < n_cols; ++i)
         if (cols[i].length != n_rows) return fail(QEH_E_INVALID, "eval columns have different lengths");
-    Utf8Rewrite uw;  // Utf8 comparisons become BOOL columns appended after the inputs (k_utf8.hip)
+    const int n_orig = n_cols;
+    FnRewrite fw;  // scalar functions become columns appended after the inputs (k_scalar_fn.hip)
+    QEH_TRY(rewrite_scalar_functions(ctx, cols, n_cols, n_rows, expr, &fw));
+    if (fw.changed) {
+        cols = fw.cols.data();
+        n_cols = (int)fw.cols.size();
+        expr = &fw.expr;
+    }
+    Utf8Rewrite uw;  // Utf8 comparisons become BOOL columns appended after those (k_utf8.hip)
     QEH_TRY(rewrite_utf8_compares(ctx, cols, n_cols, expr, &uw));
     const int n_in = n_cols;
     if (uw.changed) {
@@ -590,6 +606,10 @@ extern "C" int qeh_eval(qeh_ctx *ctx, const qeh_column *cols, int n_cols, const 
     if (ci >= n_in) {  // the whole expression was one Utf8 comparison: hand its column over
         *out = cols[ci];
         uw.temps.erase(uw.temps.begin() + (ci - n_in));
+        return QEH_OK;
+    }
+    if (ci >= n_orig && fw.is_temp(ci)) {  // the whole expression was one function: likewise
+        *out = fw.take(ci);
         return QEH_OK;
     }
     if (ci >= 0) {  // zero-copy column reference (operators.rs:15-23)

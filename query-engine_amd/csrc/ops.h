@@ -157,6 +157,32 @@ struct Utf8Rewrite {
 int rewrite_utf8_compares(qeh_ctx *ctx, const qeh_column *cols, int n_cols, const qeh_expr *e, Utf8Rewrite *out);
 bool expr_has_utf8(const qeh_expr *e, const int32_t *dtypes, int n_cols);
 
+// Scalar functions (k_scalar_fn.hip): every QEH_EX_SCALAR_FUNCTION subtree of `e`, innermost first,
+// is materialised at the function boundary -- arguments that are not leaves through qeh_eval into
+// temporaries, then the function's kernel into a temporary column appended after the inputs -- and
+// replaced by a COLUMN leaf (COALESCE: by its first argument).  Runs before rewrite_utf8_compares,
+// so UPPER(c) = 'BOB' reaches it as column-against-literal.  Owns the temporaries: temps[k] is
+// cols[n_in + k]; take() hands one over to the caller.  `n_rows`: the rows of every input column
+// (the inputs may be empty).  `changed` false means expr/cols are the inputs unchanged.
+struct FnRewrite {
+    qeh_ctx *ctx = nullptr;
+    std::vector<qeh_column> cols;
+    std::vector<qeh_expr_node> nodes;
+    qeh_expr expr{};
+    std::vector<qeh_column> temps, args;  // appended results; evaluated arguments
+    std::vector<std::unique_ptr<DevBuf>> bufs;
+    int n_in = 0;
+    bool changed = false;
+    FnRewrite() = default;
+    FnRewrite(const FnRewrite &) = delete;
+    FnRewrite &operator=(const FnRewrite &) = delete;
+    ~FnRewrite();
+    bool is_temp(int ci) const { return ci >= n_in && ci < n_in + (int)temps.size(); }
+    qeh_column take(int ci);  // is_temp(ci): the column, no longer released by the rewrite
+};
+int rewrite_scalar_functions(qeh_ctx *ctx, const qeh_column *cols, int n_cols, int64_t n_rows, const qeh_expr *e,
+                             FnRewrite *out);
+
 // Utf8 key columns (k_utf8_dict.hip): every QEH_DT_UTF8 column of `keys` is replaced in `keys` by
 // its INT32 order-preserving dictionary codes (each Utf8 column gets its own dictionary), so the
 // integer sort / group / window paths take it.  Owns the code and dictionary columns.  decode()

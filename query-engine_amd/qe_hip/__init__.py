@@ -7,8 +7,8 @@ from . import abi  # noqa: F401
 from .abi import QehError, load  # noqa: F401
 from .device import Context, DeviceColumn, agg  # noqa: F401
 from .expr import (AggregateExpr, AggregateFunction, BinaryExpr, BinaryOp, Column, Exists,  # noqa: F401
-                   InSubquery, Literal, PhysicalExpr, ScalarSubquery, ScalarValue, UnaryExpr, UnaryOp, binop, col,
-                   lit)
+                   InSubquery, Literal, PhysicalExpr, ScalarFunction, ScalarFunctionType, ScalarSubquery, ScalarValue,
+                   UnaryExpr, UnaryOp, binop, col, lit)
 from .plan import (DataSource, Filter, HashAggregate, HashJoin, IndexScan, JoinType, Limit,  # noqa: F401
                    MemoryDataSource, Projection, QueryExecutor, Scan, Sort, SubqueryScan, Window, WindowExpr,
                    WindowFunctionType)

@@ -22,6 +22,10 @@ DT_NULL, DT_BOOL, DT_INT32, DT_INT64, DT_FLOAT32, DT_FLOAT64, DT_UTF8, DT_UINT32
 
 EX_COLUMN, EX_LITERAL, EX_BINARY, EX_UNARY = 1, 2, 3, 4
 EX_SCALAR_SUBQUERY, EX_IN_SUBQUERY, EX_EXISTS = 5, 6, 7
+EX_SCALAR_FUNCTION = 8
+# enum qeh_scalar_func: the declaration order of ScalarFunctionType (physical_plan.rs:183-205)
+(FN_UPPER, FN_LOWER, FN_LENGTH, FN_CONCAT, FN_SUBSTRING, FN_TRIM, FN_REPLACE, FN_ABS, FN_CEIL, FN_FLOOR,
+ FN_ROUND, FN_SQRT, FN_POWER, FN_COALESCE, FN_NULLIF, FN_TO_TSVECTOR, FN_TO_TSQUERY) = range(17)
 (OP_ADD, OP_SUB, OP_MUL, OP_DIV, OP_MOD, OP_EQ, OP_NEQ, OP_LT, OP_LTE, OP_GT, OP_GTE,
  OP_AND, OP_OR) = range(13)
 UOP_NOT, UOP_MINUS = 0, 1

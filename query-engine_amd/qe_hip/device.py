@@ -278,8 +278,9 @@ class Context:
         n = n_rows if n_rows is not None else (len(cols[0]) if cols else 0)
         abi.check(self.lib.qeh_eval(self.h, cin, len(cols), C.byref(e), n, C.byref(out)))
         if not out.owned:  # zero-copy column reference: keep the source alive
-            src = cols[expr.index]
-            return DeviceColumn(self, out, []), src
+            while not hasattr(expr, "index"):  # COALESCE(column, ...) is its first argument, unchanged
+                expr = expr.args[0]
+            return DeviceColumn(self, out, []), cols[expr.index]
         return self._wrap(out)
 
     def hash_aggregate(self, keys: Sequence[DeviceColumn], inputs: Sequence[DeviceColumn],

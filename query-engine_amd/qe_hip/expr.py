@@ -178,6 +178,28 @@ class Exists(PhysicalExpr):
         out.append(_subquery_node(abi.EX_EXISTS, self.plan, self.negated))
 
 
+class ScalarFunctionType:
+    """`ScalarFunctionType` (physical_plan.rs:183-205), in its declaration order."""
+    Upper, Lower, Length, Concat = abi.FN_UPPER, abi.FN_LOWER, abi.FN_LENGTH, abi.FN_CONCAT
+    Substring, Trim, Replace = abi.FN_SUBSTRING, abi.FN_TRIM, abi.FN_REPLACE
+    Abs, Ceil, Floor, Round, Sqrt, Power = abi.FN_ABS, abi.FN_CEIL, abi.FN_FLOOR, abi.FN_ROUND, abi.FN_SQRT, abi.FN_POWER
+    Coalesce, Nullif = abi.FN_COALESCE, abi.FN_NULLIF
+    ToTsVector, ToTsQuery = abi.FN_TO_TSVECTOR, abi.FN_TO_TSQUERY
+
+
+@dataclass
+class ScalarFunction(PhysicalExpr):
+    """`PhysicalExpr::ScalarFunction { func, args }` (physical_plan.rs:112-116): the arguments in
+    order, then the node (op = the function, index = the number of arguments)."""
+    func: int
+    args: List[PhysicalExpr]
+
+    def _emit(self, out):
+        for a in self.args:
+            a._emit(out)
+        out.append(abi.QehExprNode(kind=abi.EX_SCALAR_FUNCTION, op=self.func, index=len(self.args)))
+
+
 @dataclass
 class AggregateExpr:
     func: int
