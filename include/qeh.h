@@ -126,18 +126,40 @@ enum qeh_expr_kind {
  *     reference's type error.  NULL exactly where an argument they read is NULL.
  *   COALESCE: its first argument, unchanged (operators.rs:249-250).
  *   SUBSTRING / TRIM / REPLACE / NULLIF: QEH_E_UNSUPPORTED with the reference's "... function not
- *     yet fully implemented"; TO_TSVECTOR / TO_TSQUERY: QEH_E_UNSUPPORTED (Unicode tokenising). */
+ *     yet fully implemented".
+ *   TO_TSVECTOR / TO_TSQUERY: only as the direct operand of a QEH_OP_TSMATCH node, where they are
+ *     evaluated as part of the match (see qeh_binop) after the reference's checks ("TO_TSVECTOR
+ *     requires 1 argument", QEH_E_INVALID; "TO_TSQUERY requires string argument", QEH_E_TYPE).
+ *     Anywhere else -- projected, compared, an argument of another function, nested inside one
+ *     another -- QEH_E_UNSUPPORTED: no tsvector string is materialised on the device. */
 enum qeh_scalar_func {
     QEH_FN_UPPER = 0, QEH_FN_LOWER = 1, QEH_FN_LENGTH = 2, QEH_FN_CONCAT = 3, QEH_FN_SUBSTRING = 4,
     QEH_FN_TRIM = 5, QEH_FN_REPLACE = 6, QEH_FN_ABS = 7, QEH_FN_CEIL = 8, QEH_FN_FLOOR = 9,
     QEH_FN_ROUND = 10, QEH_FN_SQRT = 11, QEH_FN_POWER = 12, QEH_FN_COALESCE = 13, QEH_FN_NULLIF = 14,
     QEH_FN_TO_TSVECTOR = 15, QEH_FN_TO_TSQUERY = 16
 };
-/* Same order as `BinaryOp` (physical_plan.rs:119-136; TsMatch excluded). */
+/* Same order as `BinaryOp` (physical_plan.rs:119-136).
+ *   TSMATCH (`l @@ r`, operators.rs:571-610): both operands Utf8 (else QEH_E_TYPE "@@ left operand
+ *     must be tsvector (string)" / "@@ right operand must be tsquery (string)"; a typed NULL literal
+ *     is a NullArray, not a string), result BOOL, NULL where either side is NULL.  A row is TRUE when
+ *     every term of the right side is one of the left side's tokens, by byte equality; the terms are
+ *     the right side's pieces except "&", "|" and pieces that start with '!' (so '|' does not mean
+ *     OR, "!x" is ignored and an empty query matches).  The pieces of a side depend on how the
+ *     operand is written (enum qeh_ts_mode): a plain Utf8 expression, TO_TSVECTOR(x) or
+ *     TO_TSQUERY(x), legal on either side.  A byte >= 0x80 in a non-NULL row of either side (a
+ *     literal included) is QEH_E_UNSUPPORTED: Rust lower-cases and splits by Unicode rules.
+ *     Valid wherever a scalar function is (qeh_eval / qeh_filter / qeh_filter_limit /
+ *     qeh_expr_type, anywhere in a plan); the fused entry points return QEH_E_UNSUPPORTED. */
 enum qeh_binop {
     QEH_OP_ADD = 0, QEH_OP_SUB = 1, QEH_OP_MUL = 2, QEH_OP_DIV = 3, QEH_OP_MOD = 4,
     QEH_OP_EQ = 5, QEH_OP_NEQ = 6, QEH_OP_LT = 7, QEH_OP_LTE = 8, QEH_OP_GT = 9,
-    QEH_OP_GTE = 10, QEH_OP_AND = 11, QEH_OP_OR = 12
+    QEH_OP_GTE = 10, QEH_OP_AND = 11, QEH_OP_OR = 12, QEH_OP_TSMATCH = 13
+};
+/* How one side of `@@` is cut into pieces.  White space is 0x09-0x0D and 0x20. */
+enum qeh_ts_mode {
+    QEH_TS_PLAIN = 0,    /* a Utf8 expression: white-space separated pieces, bytes as they are       */
+    QEH_TS_TSVECTOR = 1, /* TO_TSVECTOR(x): maximal runs of [0-9A-Za-z], ASCII lower-cased           */
+    QEH_TS_TSQUERY = 2   /* TO_TSQUERY(x): white-space separated pieces, ASCII lower-cased           */
 };
 /* `UnaryOp` (physical_plan.rs:138-142). */
 enum qeh_unop { QEH_UOP_NOT = 0, QEH_UOP_MINUS = 1 };
@@ -157,7 +179,8 @@ typedef struct qeh_expr_node {
                             appear in comparisons of two leaves (column / literal /
                             a function's Utf8 result), evaluated by byte-wise
                             lexicographic order, operators.rs:509-538 on
-                            StringArray, and as scalar function arguments   */
+                            StringArray, as scalar function arguments, and as
+                            the operands of QEH_OP_TSMATCH                  */
     double lit_f64;      /* FLOAT32/FLOAT64 literal                         */
 } qeh_expr_node;
 
@@ -542,6 +565,19 @@ int qeh_utf8_join_encode(qeh_ctx *ctx, const qeh_column *build, const qeh_column
  * row count; QEH_IN_SET=bitmap|hash (read per call) forces one for integer and Utf8 keys
  * (float keys always take the hash set; a forced bitmap over a range beyond 2^31 is QEH_E_INVALID). */
 int qeh_in_set(qeh_ctx *ctx, const qeh_column *probe, const qeh_column *set, int negated, qeh_column *out);
+
+/* Full-text match `doc @@ query` (BinaryOp::TsMatch, operators.rs:571-610; the rules under
+ * qeh_binop) without materialising a tsvector or tsquery string.  doc: a Utf8 column cut by
+ * doc_mode (enum qeh_ts_mode).  The query is query_col (Utf8, doc's length, per-row terms) when it
+ * is not NULL, else the literal query_lit[0 .. query_lit_len) (host bytes, read during the call),
+ * cut by query_mode.  out: an owned BOOL column of doc->length rows, NULL where doc or query_col is
+ * NULL.  A literal query of at most 64 distinct terms is scanned by k_ts_match_stream (one wave per
+ * 64 rows over their concatenated bytes); a query column, more terms, or QEH_NO_TS_STREAM set in
+ * the environment (read per call) take the row-per-lane kernel.  A byte >= 0x80 in a non-NULL row
+ * or in the literal: QEH_E_UNSUPPORTED.  Columns may carry validity bitmaps and non-zero offsets;
+ * the bytes of NULL rows are not inspected. */
+int qeh_ts_match(qeh_ctx *ctx, const qeh_column *doc, int doc_mode, const qeh_column *query_col,
+                 const char *query_lit, int64_t query_lit_len, int query_mode, qeh_column *out);
 
 /* Stable lexicographic sort -> permutation (UINT32 row ids) of the input.
  * Intended semantics of `Sort` (physical_plan.rs:40-44; executor.rs:290-297

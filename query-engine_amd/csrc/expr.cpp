@@ -10,6 +10,9 @@
 //   %             -> Int64/Int64 or Int32/Int32, "Modulo operation requires integer arrays" (:711-743)
 //   comparisons   -> coerce_numeric_types (:616-675) then arrow cmp on equal types
 //   AND / OR      -> Boolean only, "AND requires boolean arrays" / "OR ..." (:540-571)
+//   @@            -> Utf8 on both sides, "@@ left operand must be tsvector (string)" /
+//                    "@@ right operand must be tsquery (string)" (:571-583); TO_TSVECTOR / TO_TSQUERY
+//                    are typed only directly under it (:261-297)
 #include <string>
 #include <vector>
 
@@ -147,6 +150,11 @@ static int type_binary(int op, int lt, int rt, int *res, int *cl, int *cr) {
                 return fail(QEH_E_TYPE, op == QEH_OP_AND ? "AND requires boolean arrays" : "OR requires boolean arrays");
             *res = QEH_DT_BOOL;
             return QEH_OK;
+        case QEH_OP_TSMATCH:  // operators.rs:571-583: the left downcast fails first
+            if (lt != QEH_DT_UTF8) return fail(QEH_E_TYPE, "@@ left operand must be tsvector (string)");
+            if (rt != QEH_DT_UTF8) return fail(QEH_E_TYPE, "@@ right operand must be tsquery (string)");
+            *res = QEH_DT_BOOL;
+            return QEH_OK;
         default: return fail(QEH_E_UNSUPPORTED, "binary operator not supported on the device");
     }
 }
@@ -162,9 +170,47 @@ const char *scalar_fn_name(int func) {
 }
 
 bool expr_has_function(const qeh_expr *e) {
-    for (int i = 0; e && e->nodes && i < e->n_nodes; ++i)
+    for (int i = 0; e && e->nodes && i < e->n_nodes; ++i) {
         if (e->nodes[i].kind == QEH_EX_SCALAR_FUNCTION) return true;
+        if (e->nodes[i].kind == QEH_EX_BINARY && e->nodes[i].op == QEH_OP_TSMATCH) return true;
+    }
     return false;
+}
+
+static bool is_ts_fn(const qeh_expr_node &nd) {
+    return nd.kind == QEH_EX_SCALAR_FUNCTION && (nd.op == QEH_FN_TO_TSVECTOR || nd.op == QEH_FN_TO_TSQUERY);
+}
+
+bool ts_match_operands(const qeh_expr *e, std::vector<char> *marks) {
+    marks->assign(e && e->nodes && e->n_nodes > 0 ? e->n_nodes : 0, 0);
+    std::vector<int> start(marks->size());  // start[i]: first node of the subtree whose root is node i
+    for (int i = 0; i < (int)marks->size(); ++i) {
+        const qeh_expr_node &nd = e->nodes[i];
+        int n_children = 0;
+        if (nd.kind == QEH_EX_BINARY) n_children = 2;
+        else if (nd.kind == QEH_EX_UNARY || nd.kind == QEH_EX_IN_SUBQUERY) n_children = 1;
+        else if (nd.kind == QEH_EX_SCALAR_FUNCTION) n_children = nd.index > 0 ? nd.index : 0;
+        int first = i;
+        for (int c = 0; c < n_children; ++c) {
+            if (first < 1) return false;
+            first = start[first - 1];
+        }
+        start[i] = first;
+        if (nd.kind == QEH_EX_BINARY && nd.op == QEH_OP_TSMATCH) {
+            const int r = i - 1, l = start[r] - 1;  // the operands' roots
+            if (is_ts_fn(e->nodes[r])) (*marks)[r] = 1;
+            if (is_ts_fn(e->nodes[l])) (*marks)[l] = 1;
+        }
+    }
+    return true;
+}
+
+int ts_fn_type(int func, const int *at, int n_args, int *out_type) {
+    const std::string name = scalar_fn_name(func);
+    if (n_args < 1) return fail(QEH_E_INVALID, name + " requires 1 argument");
+    if (at[0] != QEH_DT_UTF8) return fail(QEH_E_TYPE, name + " requires string argument");
+    *out_type = QEH_DT_UTF8;
+    return QEH_OK;
 }
 
 // evaluate_scalar_function's checks after the arguments are evaluated (operators.rs:74-259):
@@ -218,6 +264,8 @@ int scalar_fn_type(int func, const int *at, int n_args, int *out_type) {
 int type_expr(const qeh_expr *e, const int32_t *dtypes, int n_cols, int32_t *out_type) {
     if (!e || e->n_nodes <= 0 || !e->nodes) return fail(QEH_E_INVALID, "empty expression");
     std::vector<int> ty;
+    std::vector<char> ts_operand;  // TO_TSVECTOR / TO_TSQUERY directly under an @@
+    (void)ts_match_operands(e, &ts_operand);
     for (int i = 0; i < e->n_nodes; ++i) {
         const qeh_expr_node &nd = e->nodes[i];
         switch (nd.kind) {
@@ -243,7 +291,8 @@ int type_expr(const qeh_expr *e, const int32_t *dtypes, int n_cols, int32_t *out
                 if (nd.index < 0 || (size_t)nd.index > ty.size())
                     return fail(QEH_E_INVALID, "malformed expression (scalar function arguments)");
                 int res;
-                QEH_TRY(scalar_fn_type(nd.op, ty.data() + (ty.size() - nd.index), nd.index, &res));
+                if (ts_operand[i]) QEH_TRY(ts_fn_type(nd.op, ty.data() + (ty.size() - nd.index), nd.index, &res));
+                else QEH_TRY(scalar_fn_type(nd.op, ty.data() + (ty.size() - nd.index), nd.index, &res));
                 ty.resize(ty.size() - nd.index);
                 ty.push_back(res);
                 break;
@@ -261,6 +310,13 @@ int type_expr(const qeh_expr *e, const int32_t *dtypes, int n_cols, int32_t *out
 int compile_expr(const qeh_expr *e, const int32_t *dtypes, int n_cols, DevProgram *out) {
     if (!e || e->n_nodes <= 0 || !e->nodes) return fail(QEH_E_INVALID, "empty expression");
     out->n = 0;
+    // a full-text match is materialised first, like a function (rewrite_scalar_functions ->
+    // k_ts_match.hip); refused by name before its Utf8 operands are ("Utf8 expressions ...")
+    for (int i = 0; i < e->n_nodes; ++i)
+        if (e->nodes[i].kind == QEH_EX_BINARY && e->nodes[i].op == QEH_OP_TSMATCH)
+            return fail(QEH_E_UNSUPPORTED,
+                        "full-text match (QEH_OP_TSMATCH, @@) is not part of a kernel's expression program: "
+                        "evaluate it with qeh_eval / qeh_filter or inside a plan");
     std::vector<int> ty;  // type stack (slot = depth)
     auto emit = [&](DevInstr in) -> int {
         if (out->n >= kMaxInstr)

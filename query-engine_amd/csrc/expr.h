@@ -6,6 +6,8 @@
 
 #include <stdint.h>
 
+#include <vector>
+
 #include "../../include/qeh.h"
 #include "device_common.h"
 
@@ -68,7 +70,15 @@ int type_expr(const qeh_expr *e, const int32_t *dtypes, int n_cols, int32_t *out
 // reference's messages; *out_type = its result type.
 int scalar_fn_type(int func, const int *arg_types, int n_args, int *out_type);
 const char *scalar_fn_name(int func);
+// True when `e` holds a node the expression program cannot carry and qeh_eval / qeh_filter
+// materialise first: a scalar function, or a full-text match (QEH_OP_TSMATCH).
 bool expr_has_function(const qeh_expr *e);
+// marks[i] != 0: node i is a TO_TSVECTOR / TO_TSQUERY function that is the direct operand of a
+// QEH_OP_TSMATCH node -- the only place the two are accepted (they become that side's mode).
+// False on a malformed postfix (the typing pass reports it).
+bool ts_match_operands(const qeh_expr *e, std::vector<char> *marks);
+// The checks of such an operand: arity, then the argument's type (operators.rs:261-297).
+int ts_fn_type(int func, const int *arg_types, int n_args, int *out_type);
 // Try to lower to the fast term list (only for BOOL-typed predicates).
 bool lower_to_terms(const qeh_expr *e, const int32_t *dtypes, int n_cols, PredTerms *out);
 // Index of the column a bare Column expression refers to, else -1.

@@ -6,7 +6,9 @@
 // once, innermost function first; each argument that is not a leaf goes through qeh_eval into a
 // temporary, the function's kernel writes a temporary column appended after the operator's inputs,
 // and the subtree becomes a COLUMN leaf.  What remains (arithmetic, comparisons, Utf8 comparisons
-// of the new leaves) takes the existing paths.
+// of the new leaves) takes the existing paths.  The same walk replaces every full-text match
+// (QEH_OP_TSMATCH over operands that may be wrapped in TO_TSVECTOR / TO_TSQUERY) by the BOOL column
+// of k_ts_match.hip: the wrapping function is peeled into its side's mode, nothing is materialised.
 //
 // Kernels (each under its own KernelTimer name):
 //   scalar_math      ABS / CEIL / FLOOR / ROUND / SQRT / POWER over 8-byte slots, two rows per lane
@@ -615,6 +617,73 @@ int rewrite_scalar_functions(qeh_ctx *ctx, const qeh_column *cols, int n_cols, i
     out->changed = false;
     if (!expr_has_function(e)) return QEH_OK;
     std::vector<int> start;  // start[m]: first node of the subtree whose root is output node m
+    // full-text match: a TO_TSVECTOR / TO_TSQUERY directly under an @@ is peeled into the mode of
+    // the leaf that replaces it (ts_mode[m], QEH_TS_PLAIN for every other node); the @@ node then
+    // runs the match kernel over its two operands and becomes a BOOL COLUMN leaf
+    std::vector<char> ts_operand;
+    std::vector<int> ts_mode;
+    (void)ts_match_operands(e, &ts_operand);
+    // nodes [first, second) of the output so far, evaluated: a leaf as it is, anything else
+    // through qeh_eval over the columns it reads only (one kernel sees at most kMaxCols)
+    auto eval_span = [&](int first_node, int second, FnArg *arg) -> int {
+        const qeh_expr_node *x = out->nodes.data() + first_node;
+        const int len = second - first_node;
+        if (len == 1 && x->kind == QEH_EX_LITERAL) {
+            arg->is_lit = true;
+            arg->lit = *x;
+            return QEH_OK;
+        }
+        if (len == 1 && x->kind == QEH_EX_COLUMN) {
+            if (x->index < 0 || x->index >= (int)out->cols.size())
+                return fail(QEH_E_INVALID, "Column index " + std::to_string(x->index) + " out of bounds");
+            arg->col = out->cols[x->index];
+            arg->col_index = x->index;
+            return QEH_OK;
+        }
+        std::vector<qeh_expr_node> sub(x, x + len);
+        std::vector<qeh_column> used;
+        std::vector<int> pos_of(out->cols.size(), -1);
+        for (auto &y : sub) {
+            if (y.kind != QEH_EX_COLUMN) continue;
+            if (y.index < 0 || y.index >= (int)out->cols.size())
+                return fail(QEH_E_INVALID, "Column index " + std::to_string(y.index) + " out of bounds");
+            if (pos_of[y.index] < 0) {
+                pos_of[y.index] = (int)used.size();
+                used.push_back(out->cols[y.index]);
+            }
+            y.index = pos_of[y.index];
+        }
+        const qeh_expr se{sub.data(), len};
+        qeh_column r{};
+        QEH_TRY(qeh_eval(ctx, used.data(), (int)used.size(), &se, n_rows, &r));
+        if (r.owned) out->args.push_back(r);
+        arg->col = r;
+        return QEH_OK;
+    };
+    // the subtree from node `pos` on becomes one leaf
+    auto replace_by = [&](int pos, const qeh_expr_node &leaf, int mode) {
+        out->nodes.resize(pos);
+        start.resize(pos);
+        ts_mode.resize(pos);
+        out->nodes.push_back(leaf);
+        start.push_back(pos);
+        ts_mode.push_back(mode);
+        out->changed = true;
+    };
+    // an appended column: it joins the temporaries (moved there when it was an evaluated argument)
+    auto append_column = [&](const qeh_column &c) -> qeh_expr_node {
+        for (size_t i = 0; i < out->args.size(); ++i)
+            if (out->args[i].values == c.values && out->args[i].offsets == c.offsets) {
+                out->args.erase(out->args.begin() + i);
+                break;
+            }
+        out->temps.push_back(c);
+        out->cols.push_back(c);
+        qeh_expr_node leaf{};
+        leaf.kind = QEH_EX_COLUMN;
+        leaf.index = (int32_t)out->cols.size() - 1;
+        return leaf;
+    };
     for (int i = 0; i < e->n_nodes; ++i) {
         const qeh_expr_node &nd = e->nodes[i];
         const int m = (int)out->nodes.size();
@@ -622,6 +691,31 @@ int rewrite_scalar_functions(qeh_ctx *ctx, const qeh_column *cols, int n_cols, i
         if (nd.kind == QEH_EX_BINARY) {
             if (m < 2 || start[m - 1] < 1) return fail(QEH_E_INVALID, "malformed expression (binary)");
             first = start[start[m - 1] - 1];
+            if (nd.op == QEH_OP_TSMATCH) {
+                // both operands are evaluated first, the left one's error before the right one's
+                // (operators.rs:382-383), then the two downcasts fail in that order (:571-583)
+                const int rfirst = start[m - 1];
+                FnArg side[2];
+                QEH_TRY(eval_span(first, rfirst, &side[0]));
+                QEH_TRY(eval_span(rfirst, m, &side[1]));
+                if (side[0].type() != QEH_DT_UTF8) return fail(QEH_E_TYPE, "@@ left operand must be tsvector (string)");
+                if (side[1].type() != QEH_DT_UTF8) return fail(QEH_E_TYPE, "@@ right operand must be tsquery (string)");
+                TsSide ts[2];
+                for (int k = 0; k < 2; ++k) {
+                    const int root = k == 0 ? rfirst - 1 : m - 1;
+                    ts[k].mode = ts_mode[root];
+                    if (side[k].is_lit) {
+                        ts[k].lit = (const uint8_t *)(uintptr_t)side[k].lit.lit_i64;
+                        ts[k].lit_len = side[k].lit.index;
+                    } else {
+                        ts[k].col = &side[k].col;
+                    }
+                }
+                qeh_column res{};
+                QEH_TRY(ts_match(ctx, ts[0], ts[1], n_rows, &res));
+                replace_by(first, append_column(res), QEH_TS_PLAIN);
+                continue;
+            }
         } else if (nd.kind == QEH_EX_UNARY || nd.kind == QEH_EX_IN_SUBQUERY) {
             if (m < 1) return fail(QEH_E_INVALID, "malformed expression (unary)");
             first = start[m - 1];
@@ -635,50 +729,34 @@ int rewrite_scalar_functions(qeh_ctx *ctx, const qeh_column *cols, int n_cols, i
             }
             // every argument is evaluated first: its own error wins (operators.rs:70-72)
             std::vector<FnArg> args(span.size());
-            for (size_t a = 0; a < span.size(); ++a) {
-                const qeh_expr_node *x = out->nodes.data() + span[a].first;
-                const int len = span[a].second - span[a].first;
-                if (len == 1 && x->kind == QEH_EX_LITERAL) {
-                    args[a].is_lit = true;
-                    args[a].lit = *x;
-                } else if (len == 1 && x->kind == QEH_EX_COLUMN) {
-                    if (x->index < 0 || x->index >= (int)out->cols.size())
-                        return fail(QEH_E_INVALID, "Column index " + std::to_string(x->index) + " out of bounds");
-                    args[a].col = out->cols[x->index];
-                    args[a].col_index = x->index;
+            for (size_t a = 0; a < span.size(); ++a) QEH_TRY(eval_span(span[a].first, span[a].second, &args[a]));
+            if (ts_operand[i]) {
+                // evaluated as part of the match: its argument stands for it, cut by the function's mode
+                std::vector<int> types;
+                for (auto &a : args) types.push_back(a.type());
+                int rt = 0;
+                QEH_TRY(ts_fn_type(nd.op, types.data(), (int)types.size(), &rt));
+                const int mode = nd.op == QEH_FN_TO_TSVECTOR ? QEH_TS_TSVECTOR : QEH_TS_TSQUERY;
+                if (args[0].is_lit) {
+                    replace_by(pos, args[0].lit, mode);
+                } else if (args[0].col_index >= 0) {
+                    qeh_expr_node leaf{};
+                    leaf.kind = QEH_EX_COLUMN;
+                    leaf.index = args[0].col_index;
+                    replace_by(pos, leaf, mode);
                 } else {
-                    // over the columns it reads only (one kernel sees at most kMaxCols)
-                    std::vector<qeh_expr_node> sub(x, x + len);
-                    std::vector<qeh_column> used;
-                    std::vector<int> pos_of(out->cols.size(), -1);
-                    for (auto &y : sub) {
-                        if (y.kind != QEH_EX_COLUMN) continue;
-                        if (y.index < 0 || y.index >= (int)out->cols.size())
-                            return fail(QEH_E_INVALID, "Column index " + std::to_string(y.index) + " out of bounds");
-                        if (pos_of[y.index] < 0) {
-                            pos_of[y.index] = (int)used.size();
-                            used.push_back(out->cols[y.index]);
-                        }
-                        y.index = pos_of[y.index];
-                    }
-                    const qeh_expr se{sub.data(), len};
-                    qeh_column r{};
-                    QEH_TRY(qeh_eval(ctx, used.data(), (int)used.size(), &se, n_rows, &r));
-                    if (r.owned) out->args.push_back(r);
-                    args[a].col = r;
+                    replace_by(pos, append_column(args[0].col), mode);
                 }
+                continue;
             }
             qeh_expr_node leaf{};
             QEH_TRY(apply_function(ctx, nd, args, n_rows, out, &leaf));
-            out->nodes.resize(pos);
-            start.resize(pos);
-            out->nodes.push_back(leaf);
-            start.push_back(pos);
-            out->changed = true;
+            replace_by(pos, leaf, QEH_TS_PLAIN);
             continue;
         }
         out->nodes.push_back(nd);
         start.push_back(first);
+        ts_mode.push_back(QEH_TS_PLAIN);
     }
     QEH_HIP(hipStreamSynchronize(ctx->stream));  // literal host bytes are the caller's
     out->expr.nodes = out->nodes.data();

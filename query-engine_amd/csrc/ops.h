@@ -160,7 +160,9 @@ bool expr_has_utf8(const qeh_expr *e, const int32_t *dtypes, int n_cols);
 // Scalar functions (k_scalar_fn.hip): every QEH_EX_SCALAR_FUNCTION subtree of `e`, innermost first,
 // is materialised at the function boundary -- arguments that are not leaves through qeh_eval into
 // temporaries, then the function's kernel into a temporary column appended after the inputs -- and
-// replaced by a COLUMN leaf (COALESCE: by its first argument).  Runs before rewrite_utf8_compares,
+// replaced by a COLUMN leaf (COALESCE: by its first argument).  A QEH_OP_TSMATCH subtree, its
+// TO_TSVECTOR / TO_TSQUERY operands included, becomes the BOOL column of ts_match the same way
+// (an operand that is not a leaf goes through qeh_eval first).  Runs before rewrite_utf8_compares,
 // so UPPER(c) = 'BOB' reaches it as column-against-literal.  Owns the temporaries: temps[k] is
 // cols[n_in + k]; take() hands one over to the caller.  `n_rows`: the rows of every input column
 // (the inputs may be empty).  `changed` false means expr/cols are the inputs unchanged.
@@ -182,6 +184,18 @@ struct FnRewrite {
 };
 int rewrite_scalar_functions(qeh_ctx *ctx, const qeh_column *cols, int n_cols, int64_t n_rows, const qeh_expr *e,
                              FnRewrite *out);
+
+// Full-text match `doc @@ query` (k_ts_match.hip, qeh_ts_match): one side = a Utf8 column, or a
+// literal's host bytes (col == nullptr), cut into pieces by `mode` (enum qeh_ts_mode).  *out: an
+// owned BOOL column of n rows, bit-packed as k_utf8_cmp writes it, NULL where a column side is.
+// rewrite_scalar_functions replaces every QEH_OP_TSMATCH subtree by such a column.
+struct TsSide {
+    const qeh_column *col = nullptr;
+    const uint8_t *lit = nullptr;
+    int64_t lit_len = 0;
+    int mode = QEH_TS_PLAIN;
+};
+int ts_match(qeh_ctx *ctx, const TsSide &doc, const TsSide &query, int64_t n, qeh_column *out);
 
 // Utf8 key columns (k_utf8_dict.hip): every QEH_DT_UTF8 column of `keys` is replaced in `keys` by
 // its INT32 order-preserving dictionary codes (each Utf8 column gets its own dictionary), so the

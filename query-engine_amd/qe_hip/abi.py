@@ -27,7 +27,8 @@ EX_SCALAR_FUNCTION = 8
 (FN_UPPER, FN_LOWER, FN_LENGTH, FN_CONCAT, FN_SUBSTRING, FN_TRIM, FN_REPLACE, FN_ABS, FN_CEIL, FN_FLOOR,
  FN_ROUND, FN_SQRT, FN_POWER, FN_COALESCE, FN_NULLIF, FN_TO_TSVECTOR, FN_TO_TSQUERY) = range(17)
 (OP_ADD, OP_SUB, OP_MUL, OP_DIV, OP_MOD, OP_EQ, OP_NEQ, OP_LT, OP_LTE, OP_GT, OP_GTE,
- OP_AND, OP_OR) = range(13)
+ OP_AND, OP_OR, OP_TSMATCH) = range(14)
+TS_PLAIN, TS_TSVECTOR, TS_TSQUERY = 0, 1, 2  # enum qeh_ts_mode: how one side of @@ is cut into pieces
 UOP_NOT, UOP_MINUS = 0, 1
 AGG_COUNT, AGG_SUM, AGG_AVG, AGG_MIN, AGG_MAX = range(5)
 GEN_UNIFORM_MOD, GEN_UNIT_F64, GEN_PERMUTATION, GEN_SPARSE_KEY = 0, 1, 2, 3
@@ -118,6 +119,7 @@ SIGNATURES = {
     "qeh_utf8_dict_encode": (I, [P, COLP, COLP, COLP]),
     "qeh_utf8_join_encode": (I, [P, COLP, COLP, COLP, COLP, C.POINTER(I64)]),
     "qeh_in_set": (I, [P, COLP, COLP, I, COLP]),
+    "qeh_ts_match": (I, [P, COLP, I, COLP, C.c_char_p, I64, I, COLP]),
     "qeh_sort_indices": (I, [P, COLP, I, C.POINTER(C.c_int8), COLP]),
     "qeh_sort_indices_limit": (I, [P, COLP, I, C.POINTER(C.c_int8), C.c_int64, COLP]),
     "qeh_sort_indices_nulls":(I, [P, COLP, I, C.POINTER(C.c_int8), C.POINTER(C.c_int8), COLP]),

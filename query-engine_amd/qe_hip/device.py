@@ -648,6 +648,20 @@ class Context:
         abi.check(self.lib.qeh_in_set(self.h, C.byref(probe.c), C.byref(set.c), 1 if negated else 0, C.byref(out)))
         return self._wrap(out)
 
+    def ts_match(self, doc: DeviceColumn, query, doc_mode: int = abi.TS_PLAIN,
+                 query_mode: int = abi.TS_PLAIN) -> DeviceColumn:
+        """qeh_ts_match: `doc @@ query` as a BOOL column, NULL where a side is.  `query` is a Utf8
+        DeviceColumn (per-row terms) or a literal (str / bytes); the modes (abi.TS_PLAIN /
+        TS_TSVECTOR / TS_TSQUERY) say how each side is cut into pieces."""
+        out = abi.QehColumn()
+        if isinstance(query, DeviceColumn):
+            abi.check(self.lib.qeh_ts_match(self.h, C.byref(doc.c), doc_mode, C.byref(query.c), None, 0, query_mode,
+                                            C.byref(out)))
+        else:
+            b = query.encode() if isinstance(query, str) else bytes(query)
+            abi.check(self.lib.qeh_ts_match(self.h, C.byref(doc.c), doc_mode, None, b, len(b), query_mode, C.byref(out)))
+        return self._wrap(out)
+
     def sort_indices(self, keys: Sequence[DeviceColumn], ascending: Sequence[bool]) -> DeviceColumn:
         ck = self._cols(keys)
         asc = (C.c_int8 * max(len(keys), 1))(*[1 if a else 0 for a in ascending])

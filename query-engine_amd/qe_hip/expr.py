@@ -48,6 +48,7 @@ class BinaryOp:
     Add, Subtract, Multiply, Divide, Modulo = abi.OP_ADD, abi.OP_SUB, abi.OP_MUL, abi.OP_DIV, abi.OP_MOD
     Equal, NotEqual, Less, LessEqual = abi.OP_EQ, abi.OP_NEQ, abi.OP_LT, abi.OP_LTE
     Greater, GreaterEqual, And, Or = abi.OP_GT, abi.OP_GTE, abi.OP_AND, abi.OP_OR
+    TsMatch = abi.OP_TSMATCH  # `@@`: operands Utf8, each optionally wrapped in ToTsVector / ToTsQuery
 
 
 class UnaryOp:

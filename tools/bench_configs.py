@@ -30,16 +30,20 @@
              1e8 probe keys against 1e7 sparse 64-bit keys (hash-set form); beside each the byte floor (8 B
              read + 1 bit written per row at 8 TB/s) and the closest operator there was before,
              hash_join_inner of the same probe against the same (distinct) set emitting the probe key only
+  tsmatch    to_tsvector(doc) @@ to_tsquery('gpu & kernel') over 1e7 documents of about 64 bytes: the stream
+             kernel against the row-per-lane kernel (QEH_NO_TS_STREAM=1), interleaved, with GB/s over the
+             bytes read
   cfg4leg    config 4's per-rank device leg at N = 8 (fused filter + 8-way exchange pass over 1e9
              rows, the dim shard's exchange pass, the local join of what the rank receives)
 
 Prints one JSON line per config: rows/s, ms per run, algorithmic GB/s and
 fraction of 8 TB/s, and the oracle's rows/s on a bounded sample (1 thread).
-usage: python tools/bench_configs.py [--only cfg2,cfg3,cfg5,window,filter,limit,plan,left,full,merge,encode,partition,utf8_groupby,utf8_sort,utf8_join,topk,semi] [--scale 1.0]
+usage: python tools/bench_configs.py [--only cfg2,cfg3,cfg5,window,filter,limit,plan,left,full,merge,encode,partition,utf8_groupby,utf8_sort,utf8_join,topk,semi,tsmatch] [--scale 1.0]
 """
 import argparse
 import json
 import os
+import re
 import sys
 import time
 
@@ -950,6 +954,83 @@ def cfg_semi(ctx, scale):
         del probe, sset
 
 
+TS_KERNELS = ["ts_match_stream", "ts_match_rows"]
+
+
+def ts_documents(n, block=100_000):
+    """n documents of about 64 bytes as (int32 offsets, uint8 bytes): 7 to 11 words of a 32-word
+    vocabulary in mixed case, joined by mixed separators.  One block of `block` documents is drawn
+    and repeated (each repeat lies at its own addresses, so nothing is re-read from a cache)."""
+    rng = np.random.default_rng(SEED)
+    vocab = ["gpu", "kernel", "wave", "lds", "cache", "vector", "scalar", "memory", "stream", "query", "index", "token",
+             "match", "text", "search", "engine", "column", "batch", "filter", "join", "hash", "sort", "plan", "node",
+             "GPU", "Kernel", "Wave64", "LDS", "Query", "hbm3e", "x86", "mi355x"]
+    seps = [" ", " ", " ", ", ", "\t", ". ", "_", "-", "\n", "  "]
+    docs = []
+    for _ in range(min(block, n)):
+        k = int(rng.integers(7, 12))
+        w = rng.integers(0, len(vocab), k)
+        s = rng.integers(0, len(seps), k)
+        docs.append("".join(vocab[a] + seps[b] for a, b in zip(w, s)).encode())
+    lens = np.array([len(d) for d in docs], np.int64)
+    reps = -(-n // len(docs))
+    data = np.tile(np.frombuffer(b"".join(docs), np.uint8), reps)
+    offs = np.zeros(reps * len(docs) + 1, np.int64)
+    offs[1:] = np.cumsum(np.tile(lens, reps))
+    assert offs[n] < 2 ** 31
+    return offs[:n + 1].astype(np.int32), data[:offs[n]], docs
+
+
+def cfg_tsmatch(ctx, scale):
+    """to_tsvector(doc) @@ to_tsquery('gpu & kernel') over 1e7 documents through qeh_eval: the stream
+    kernel (k_ts_match_stream) against the row-per-lane kernel (QEH_NO_TS_STREAM=1), interleaved in
+    this process, one warm-up and 5 timed calls each, medians of wall and of kernel time; GB/s over the bytes read (values + offsets;
+    the column has no validity)."""
+    from qe_hip import ScalarFunction, ScalarFunctionType as F
+    n = int(1e7 * scale)
+    offs, data, docs = ts_documents(n)
+    doc = upload_utf8_raw(ctx, offs, data)
+    expr = binop(ScalarFunction(F.ToTsVector, [col(0)]), BinaryOp.TsMatch, ScalarFunction(F.ToTsQuery, [lit("gpu & kernel")]))
+    sides = {"stream": {}, "rows": {"QEH_NO_TS_STREAM": "1"}}
+    wall = {s: [] for s in sides}
+    kms = {s: {k: [] for k in TS_KERNELS} for s in sides}  # per timed call
+    selected = {}
+    ctx.timing(True)
+    for rep in range(6):  # rep 0 warms both sides up
+        for side, env in sides.items():
+            os.environ.pop("QEH_NO_TS_STREAM", None)
+            os.environ.update(env)
+            ctx.timing_reset()
+            ctx.sync()
+            t0 = time.perf_counter()
+            out = ctx.eval([doc], expr)
+            ctx.sync()
+            dt = time.perf_counter() - t0
+            if rep:
+                wall[side].append(dt * 1e3)
+                for kn in TS_KERNELS:
+                    kms[side][kn].append(ctx.kernel_time(kn)[0])
+            else:
+                selected[side] = int(out.to_numpy()[0].sum())
+            out.release()
+    ctx.timing(False)
+    os.environ.pop("QEH_NO_TS_STREAM", None)
+    alg = float(data.nbytes + offs.nbytes)
+    sample = sum(1 for d in docs if {b"gpu", b"kernel"} <= set(re.findall(rb"[0-9a-z]+", d.lower())))
+    res = {}
+    for side, kern in (("stream", "ts_match_stream"), ("rows", "ts_match_rows")):
+        med = {k: float(np.median(v)) for k, v in kms[side].items()}
+        ms = med[kern]
+        res[side] = {"wall_ms_median": float(np.median(wall[side])), "kernel_ms_median": ms, "kernels_ms_median": med,
+                     "GBs": alg / (ms * 1e-3) / 1e9 if ms else None, "rows_true": selected[side]}
+    line(f"tsmatch to_tsvector(doc) @@ to_tsquery('gpu & kernel'), {n} rows, {data.nbytes / n:.1f} B/doc", n,
+         res["stream"]["wall_ms_median"] * 1e-3, alg, res["stream"]["kernel_ms_median"], "k_ts_match_stream", None,
+         {"stream": res["stream"], "rows_kernel": res["rows"], "byte_floor_ms": alg / (PEAK * 1e9) * 1e3,
+          "kernel_speedup_stream_over_rows": res["rows"]["kernel_ms_median"] / res["stream"]["kernel_ms_median"]
+          if res["stream"]["kernel_ms_median"] else None,
+          "true_share_of_first_block_on_host": sample / len(docs), "both_kernels_agree": selected["stream"] == selected["rows"]})
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--only", default="cfg2,cfg3,cfg5,filter")
@@ -966,7 +1047,7 @@ def main():
          "merge": cfg_merge, "encode": cfg_encode, "shapes": cfg_metric_shapes, "partition": cfg_partition, "cfg3w": cfg3_wide, "window": cfg_window,
          "cfg4leg": cfg4_leg, "cfg4items": cfg4_items_leg, "cfg5leg": cfg5_leg,
          "window_lsd": cfg_window_lsd, "utf8_groupby": cfg_utf8_groupby, "utf8_sort": cfg_utf8_sort, "utf8_join": cfg_utf8_join,
-         "topk": cfg_topk, "semi": cfg_semi}[name](ctx, args.scale)
+         "topk": cfg_topk, "semi": cfg_semi, "tsmatch": cfg_tsmatch}[name](ctx, args.scale)
         ctx.sync()
         abi.check(ctx.lib.qeh_pool_trim(ctx.h))
     ctx.close()
