@@ -423,7 +423,7 @@ static uint64_t mix(uint64_t k);
 
 /* partition.rs:151-212: per row, compute_row_hash (:292-316, NULL cells skip the hasher) and push
  * the row onto partition (hash % n); the partitions are then taken in order (partition-major,
- * input order inside each).  Hash: the device's (k_hash_ids_multi in k_sort.hip). */
+ * input order inside each).  Hash: the device's (k_hash_ids_multi in k_partition.hip). */
 int qo_partition_hash(const qo_col *keys, int n_keys, int n_parts, int64_t *counts, uint32_t *out_perm) {
     if (n_keys < 1 || n_parts < 1) return err(QEH_E_INVALID, "qo_partition_hash: bad argument");
     const int64_t n = keys[0].length;

@@ -28,6 +28,7 @@
 
 #include "../../include/qeh_plan.h"
 #include "ops.h"
+#include "sort.h"
 
 namespace qeh {
 int hash_aggregate_filtered(qeh_ctx *ctx, const qeh_column *keys, int n_keys, const qeh_column *agg_inputs,

@@ -1,5 +1,5 @@
 // Fast-path column tiles shared by the fused join-aggregate (k_aggregate.hip) and the fused
-// filter + exchange pass (k_sort.hip): non-null 8-byte columns read as 16-B pairs, every load of a
+// filter + exchange pass (k_partition.hip): non-null 8-byte columns read as 16-B pairs, every load of a
 // tile issued before the term predicate is evaluated.
 #pragma once
 #include "agg.h"

@@ -17,6 +17,7 @@
 
 #include "device_common.h"
 #include "ops.h"
+#include "sort.h"
 
 namespace qeh {
 

@@ -1,16 +1,11 @@
-// SortExec, ROW_NUMBER() window and hash partitioning: LSD radix sort with
-// LDS histograms producing a stable permutation.
+// SortExec: LSD radix sort with LDS histograms producing a stable permutation, and the
+// payload-carrying sort behind Merge::sorted.  What other units use of it is declared in sort.h.
 //
-// Reference: execute_sort is the identity (crates/query-executor/src/executor.rs:290-297)
-// and the Window arm passes its input through (executor.rs:76-80), so the
-// semantics are the intended ones of SURVEY.md §8.0: stable lexicographic sort
+// Reference: execute_sort is the identity (crates/query-executor/src/executor.rs:290-297),
+// so the semantics are the intended ones of SURVEY.md §8.0: stable lexicographic sort
 // by `exprs` with a per-key ascending flag, NULLs first (arrow SortOptions
 // default; the only explicit null ordering in the tree is
-// distributed/operators.rs:97-104), floats by totalOrder; ROW_NUMBER numbers
-// rows 1.. within each PARTITION BY group in ORDER BY order, ties by input
-// position (docs/WINDOW_FUNCTIONS.md:44-65), output aligned to input order.
-// Hash partitioning follows Partitioner::partition_by_hash
-// (crates/query-distributed/src/partition.rs:151-212) with a device hash.
+// distributed/operators.rs:97-104), floats by totalOrder.
 //
 // Key encoding: each key column becomes an unsigned integer in [0, 2^bits):
 // NULL -> 0, value -> (ordered(x) - min + 1) ascending or (max - ordered(x) + 1)
@@ -24,26 +19,14 @@
 #include <string>
 #include <vector>
 
-#include "../../include/qeh_plan.h"
-#include "device_common.h"
-#include "expr_device.h"
-#include "fast_tile.h"
-#include "ops.h"
+#include "radix_device.h"
+#include "sort.h"
 
 namespace qeh {
-
-constexpr int kRadixBits = 8;
-constexpr int kRadix = 1 << kRadixBits;
 
 struct KeyStats {
     int64_t mn, mx;
 };
-
-__device__ __forceinline__ int64_t ordered_key(const ColRef &c, int64_t row) {
-    const int64_t x = load_i64(c, row);
-    if (c.dtype == QEH_DT_FLOAT32 || c.dtype == QEH_DT_FLOAT64) return f64_order_key(as_f64(x));
-    return x;
-}
 
 constexpr int kRsMaxSegs = 16;  // Merge::sorted partitions read in place (RsEncode, KeySegs)
 
@@ -174,37 +157,7 @@ __global__ void k_encode(ColRef c, const uint32_t *__restrict__ perm, int64_t n,
 // inside a tile wave w owns the contiguous run [w*64*kRsIpt, (w+1)*64*kRsIpt)
 // and its item j is element w*64*kRsIpt + j*64 + lane, so (wave, j, lane) is
 // input order and every load is a full 512-byte wave line.  hist is digit-major
-// [kRadix][nblocks].
-constexpr int kRsIpt = 8;
-constexpr int kRsThreads = 1024;
-constexpr int kRsSTile = kRsThreads * kRsIpt;  // 8192
-
-// lanes of this wave whose digit equals mine (wave64 has no match_any: 8 ballots)
-__device__ __forceinline__ uint64_t digit_peers(uint32_t dg, bool live) {
-    uint64_t peers = __ballot(live);
-#pragma unroll
-    for (int b = 0; b < kRadixBits; ++b) {
-        const uint64_t m = __ballot((dg >> b) & 1);
-        peers &= ((dg >> b) & 1) ? m : ~m;
-    }
-    return peers;
-}
-
-// Stable rank of this lane's row among the rows of digit dg ranked so far by this wave (wc = the
-// wave's counters): one returning LDS atomic when the device serves a wave's lanes in lane order
-// (AT, the default after the lds_atomic_rank_ok self-check), else ballot peers; dead lanes get 0.
-template <bool AT>
-__device__ __forceinline__ uint32_t tile_rank(uint32_t *wc, uint32_t dg, bool live) {
-    if constexpr (AT) {
-        return live ? atomicAdd(&wc[dg], 1u) : 0u;
-    } else {
-        const uint32_t d = live ? dg : 0u;
-        const uint64_t peers = digit_peers(d, live);
-        const uint32_t before = wc[d];
-        if (live && mbcnt(peers) == 0) wc[d] = before + (uint32_t)popc64(peers);
-        return live ? before + mbcnt(peers) : 0u;
-    }
-}
+// [kRadix][nblocks].  The tile constants and the in-tile ranking are in radix_device.h.
 
 // The payload sort's first pass reads the raw key column and encodes on load (KES = 4 / 8: Int32 /
 // Int64 values) instead of a separate encode pass; KES = 0 reads the codes.
@@ -444,10 +397,6 @@ __global__ __launch_bounds__(kRsThreads) void k_rs_hist_u8(const uint8_t *__rest
 // issued before the current tile is ranked (LDS-only barriers below do not
 // wait for them).
 
-__device__ __forceinline__ void lds_barrier() {
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-}
-
 // The payload sort's last pass writes the decoded key column itself (DEC): code -> Int64 / Int32 value
 // as rs_load_key's inverse, and one valid byte per row for the bitmap packed afterwards.
 struct RsDecode {
@@ -593,456 +542,78 @@ __global__ __launch_bounds__(kRsThreads) void k_rs_scatter(const KeyT *__restric
     }
 }
 
-// Partition move (the device side of Exchange): one stable pass over u8 partition ids that
-// carries up to 4 non-null 8-byte payload columns to their partition-major positions, with the
-// same tile ranking and run-contiguous writes as k_rs_scatter — instead of a permutation
-// followed by one gather per column (a gather re-reads every source line once per partition).
-constexpr int kPmMaxCols = 4;
-constexpr int kPmIpt = 4;
-constexpr int kPmTile = kRsThreads * kPmIpt;  // 4096 rows: ids + 4 columns fit in LDS
-
-struct PmCols {
-    const uint64_t *src[kPmMaxCols];
-    uint64_t *dst[kPmMaxCols];
-    int32_t n;
-};
-
-// Rows whose id is >= `drop` (the filtered-out rows of a fused filter + exchange) are ranked last
-// and not written.
-template <int NC, bool AT = true>
-__global__ __launch_bounds__(kRsThreads) void k_part_scatter(const uint8_t *__restrict__ ids, int64_t n, int64_t seg,
-                                                             const uint64_t *__restrict__ offs, int nblocks, PmCols cols,
-                                                             uint32_t drop) {
-    constexpr int W = kRsThreads / 64;
-    constexpr int DW = kRadix / 64;
-    __shared__ uint64_t s_val[NC > 0 ? NC : 1][kPmTile];
-    __shared__ uint8_t s_id[kPmTile];
-    __shared__ uint32_t wcnt[W][kRadix];
-    __shared__ uint32_t loc[kRadix];
-    __shared__ uint32_t tot_s[kRadix];
-    __shared__ uint32_t wsum[DW];
-    __shared__ uint64_t run[kRadix];
-    const int t = threadIdx.x, wave = t >> 6, lane = t & 63;
-    if (t < kRadix) run[t] = offs[(int64_t)t * nblocks + blockIdx.x];
-    const int64_t lo = (int64_t)blockIdx.x * seg, hi = lo + seg < n ? lo + seg : n;
-    // the next tile's ids and columns are loaded into registers while this tile is ranked, staged
-    // and written (the barriers below order LDS only, so those loads stay in flight)
-    uint32_t dgn[kPmIpt];
-    uint64_t vn[kPmIpt][NC > 0 ? NC : 1];
-    auto load = [&](int64_t c0) {
-        const int64_t base = c0 + (int64_t)wave * 64 * kPmIpt + lane;
-#pragma unroll
-        for (int j = 0; j < kPmIpt; ++j) {
-            const int64_t i = base + j * 64;
-            const int64_t ii = i < hi ? i : hi - 1;
-            dgn[j] = ids[ii];
-#pragma unroll
-            for (int c = 0; c < NC; ++c) vn[j][c] = __builtin_nontemporal_load(&cols.src[c][ii]);
-        }
-    };
-    if (lo < hi) load(lo);
-    __syncthreads();  // run[]
-    for (int64_t c0 = lo; c0 < hi; c0 += kPmTile) {
-        for (int i = t; i < W * kRadix; i += kRsThreads) (&wcnt[0][0])[i] = 0;
-        const int64_t base = c0 + (int64_t)wave * 64 * kPmIpt + lane;
-        uint32_t dg[kPmIpt];
-        uint64_t v[kPmIpt][NC > 0 ? NC : 1];
-#pragma unroll
-        for (int j = 0; j < kPmIpt; ++j) {
-            dg[j] = dgn[j];
-#pragma unroll
-            for (int c = 0; c < NC; ++c) v[j][c] = vn[j][c];
-        }
-        if (c0 + kPmTile < hi) load(c0 + kPmTile);
-        lds_barrier();
-        uint32_t rk[kPmIpt];
-#pragma unroll
-        for (int j = 0; j < kPmIpt; ++j) {
-            const bool live = base + j * 64 < hi;
-            rk[j] = tile_rank<AT>(wcnt[wave], dg[j], live);  // stable
-        }
-        lds_barrier();
-        uint32_t tot = 0, incl = 0;
-        if (t < kRadix) {
-#pragma unroll
-            for (int w = 0; w < W; ++w) {
-                const uint32_t c = wcnt[w][t];
-                wcnt[w][t] = tot;
-                tot += c;
-            }
-            tot_s[t] = tot;
-            incl = wave_incl_scan(tot);
-            if (lane == 63) wsum[wave] = incl;
-        }
-        lds_barrier();
-        if (t < kRadix) {
-            uint32_t wbase = 0;
-#pragma unroll
-            for (int w = 0; w < DW; ++w) wbase += w < wave ? wsum[w] : 0;
-            loc[t] = wbase + incl - tot;
-        }
-        lds_barrier();
-#pragma unroll
-        for (int j = 0; j < kPmIpt; ++j) {
-            if (base + j * 64 < hi) {
-                const uint32_t p = loc[dg[j]] + wcnt[wave][dg[j]] + rk[j];
-                s_id[p] = (uint8_t)dg[j];
-#pragma unroll
-                for (int c = 0; c < NC; ++c) s_val[c][p] = v[j][c];
-            }
-        }
-        lds_barrier();
-        const int cnt = (int)(hi - c0 < kPmTile ? hi - c0 : kPmTile);
-        for (int p = t; p < cnt; p += kRsThreads) {
-            const uint32_t d = s_id[p];
-            if (d >= drop) continue;
-            const uint64_t pos = run[d] + (uint64_t)(p - (int)loc[d]);
-#pragma unroll
-            for (int c = 0; c < NC; ++c) cols.dst[c][pos] = s_val[c][p];
-        }
-        lds_barrier();
-        if (t < kRadix) run[t] += tot_s[t];
-    }
+void launch_hist_u8(qeh_ctx *ctx, const uint8_t *ids, int64_t n, int64_t seg, uint32_t *hist, int nblocks) {
+    hipLaunchKernelGGL(k_rs_hist_u8, dim3(nblocks), dim3(kRsThreads), 0, ctx->stream, ids, n, seg, hist, nblocks);
 }
 
-// k_part_scatter for at most kPsDig partitions (an Exchange to the GPUs of one node, config 4's 8):
-// the same stable, run-contiguous placement with the bookkeeping sized to the partitions instead of
-// 256 digits (16 per-wave counters, a 16-lane scan), 8192-row tiles for up to two columns, and rows
-// with an id >= drop (the filtered-out rows) neither ranked nor staged, so the write loop covers only
-// the rows that move.
-constexpr int kPsDig = 16;
-template <int NC, bool AT = true>
-__global__ __launch_bounds__(kRsThreads) void k_part_scatter_small(const uint8_t *__restrict__ ids, int64_t n, int64_t seg,
-                                                                   const uint64_t *__restrict__ offs, int nblocks, PmCols cols,
-                                                                   uint32_t drop) {
-    constexpr int W = kRsThreads / 64;
-    constexpr int IPT = NC <= 2 ? 8 : 4;
-    constexpr int TILE = kRsThreads * IPT;
-    __shared__ uint64_t s_val[NC > 0 ? NC : 1][TILE];
-    __shared__ uint8_t s_id[TILE];
-    __shared__ uint32_t wcnt[W][kPsDig];  // per-wave counts, then per-wave starts inside the partition
-    __shared__ uint32_t loc[kPsDig], tot_s[kPsDig + 1];
-    __shared__ uint64_t run[kPsDig];
-    const int t = threadIdx.x, wave = t >> 6, lane = t & 63;
-    if (drop > (uint32_t)kPsDig) drop = kPsDig;
-    if (t < kPsDig) run[t] = offs[(int64_t)t * nblocks + blockIdx.x];
-    const int64_t lo = (int64_t)blockIdx.x * seg, hi = lo + seg < n ? lo + seg : n;
-    uint32_t dgn[IPT];
-    uint64_t vn[IPT][NC > 0 ? NC : 1];
-    auto load = [&](int64_t c0) {
-        const int64_t base = c0 + (int64_t)wave * 64 * IPT + lane;
-#pragma unroll
-        for (int j = 0; j < IPT; ++j) {
-            const int64_t i = base + j * 64;
-            const int64_t ii = i < hi ? i : hi - 1;
-            dgn[j] = ids[ii];
-#pragma unroll
-            for (int c = 0; c < NC; ++c) vn[j][c] = __builtin_nontemporal_load(&cols.src[c][ii]);
-        }
-    };
-    if (lo < hi) load(lo);
-    __syncthreads();  // run[]
-    for (int64_t c0 = lo; c0 < hi; c0 += TILE) {
-        if (t < W * kPsDig) (&wcnt[0][0])[t] = 0u;
-        const int64_t base = c0 + (int64_t)wave * 64 * IPT + lane;
-        uint32_t dg[IPT];
-        uint64_t v[IPT][NC > 0 ? NC : 1];
-#pragma unroll
-        for (int j = 0; j < IPT; ++j) {
-            dg[j] = dgn[j];
-#pragma unroll
-            for (int c = 0; c < NC; ++c) v[j][c] = vn[j][c];
-        }
-        if (c0 + TILE < hi) load(c0 + TILE);
-        lds_barrier();
-        uint32_t rk[IPT];
-        bool mv[IPT];
-#pragma unroll
-        for (int j = 0; j < IPT; ++j) {
-            mv[j] = base + j * 64 < hi && dg[j] < drop;
-            rk[j] = tile_rank<AT>(wcnt[wave], dg[j], mv[j]);  // stable
-        }
-        lds_barrier();
-        if (t < 64) {  // lane d < kPsDig: per-wave starts inside partition d, its tile total, the scan
-            uint32_t tot = 0;
-            if (lane < kPsDig) {
-#pragma unroll
-                for (int w = 0; w < W; ++w) {
-                    const uint32_t c = wcnt[w][lane];
-                    wcnt[w][lane] = tot;
-                    tot += c;
-                }
-            }
-            const uint32_t incl = wave_incl_scan(tot);
-            if (lane < kPsDig) loc[lane] = incl - tot, tot_s[lane] = tot;
-            if (lane == kPsDig - 1) tot_s[kPsDig] = incl;  // rows that move in this tile
-        }
-        lds_barrier();
-#pragma unroll
-        for (int j = 0; j < IPT; ++j) {
-            if (mv[j]) {
-                const uint32_t p = loc[dg[j]] + wcnt[wave][dg[j]] + rk[j];
-                s_id[p] = (uint8_t)dg[j];
-#pragma unroll
-                for (int c = 0; c < NC; ++c) s_val[c][p] = v[j][c];
-            }
-        }
-        lds_barrier();
-        const int cnt = (int)tot_s[kPsDig];
-        for (int p = t; p < cnt; p += kRsThreads) {
-            const uint32_t d = s_id[p];
-            const uint64_t pos = run[d] + (uint64_t)(p - (int)loc[d]);
-#pragma unroll
-            for (int c = 0; c < NC; ++c) cols.dst[c][pos] = s_val[c][p];
-        }
-        lds_barrier();
-        if (t < kPsDig) run[t] += tot_s[t];
-    }
-}
-
-// The inverse of k_part_scatter_small (qeh_partition_hash_unmove): the same stable ranking of each
-// tile's rows by partition, but every row reads its value from the partition-major column at the
-// position the forward move gave it (run start + its rank in the partition) and writes it at its own
-// input position.  A stable partition places row i at (rows of lower partitions) + (rows of its
-// partition before i) whatever the tiling, so this reproduces any stable forward move.
-template <int NC, bool AT = true>
-__global__ __launch_bounds__(kRsThreads) void k_part_gather_small(const uint8_t *__restrict__ ids, int64_t n, int64_t seg,
-                                                                  const uint64_t *__restrict__ offs, int nblocks, PmCols cols) {
-    constexpr int W = kRsThreads / 64;
-    constexpr int IPT = 8;
-    constexpr int TILE = kRsThreads * IPT;
-    __shared__ uint32_t wcnt[W][kPsDig];
-    __shared__ uint32_t tot_s[kPsDig];
-    __shared__ uint64_t run[kPsDig];
-    const int t = threadIdx.x, wave = t >> 6, lane = t & 63;
-    if (t < kPsDig) run[t] = offs[(int64_t)t * nblocks + blockIdx.x];
-    const int64_t lo = (int64_t)blockIdx.x * seg, hi = lo + seg < n ? lo + seg : n;
-    __syncthreads();  // run[]
-    for (int64_t c0 = lo; c0 < hi; c0 += TILE) {
-        if (t < W * kPsDig) (&wcnt[0][0])[t] = 0u;
-        const int64_t base = c0 + (int64_t)wave * 64 * IPT + lane;
-        uint32_t dg[IPT];
-#pragma unroll
-        for (int j = 0; j < IPT; ++j) {
-            const int64_t i = base + j * 64;
-            dg[j] = ids[i < hi ? i : hi - 1];
-        }
-        lds_barrier();
-        uint32_t rk[IPT];
-        bool live[IPT];
-#pragma unroll
-        for (int j = 0; j < IPT; ++j) {
-            live[j] = base + j * 64 < hi;
-            rk[j] = tile_rank<AT>(wcnt[wave], dg[j], live[j]);  // stable, as the forward move
-        }
-        lds_barrier();
-        if (t < kPsDig) {  // thread d: per-wave starts inside partition d, its tile total
-            uint32_t tot = 0;
-#pragma unroll
-            for (int w = 0; w < W; ++w) {
-                const uint32_t c = wcnt[w][t];
-                wcnt[w][t] = tot;
-                tot += c;
-            }
-            tot_s[t] = tot;
-        }
-        lds_barrier();
-        uint64_t v[IPT][NC];
-#pragma unroll
-        for (int j = 0; j < IPT; ++j) {
-            const uint64_t pos = live[j] ? run[dg[j]] + wcnt[wave][dg[j]] + rk[j] : 0;
-#pragma unroll
-            for (int c = 0; c < NC; ++c) v[j][c] = live[j] ? cols.src[c][pos] : 0;
-        }
-#pragma unroll
-        for (int j = 0; j < IPT; ++j)
-            if (live[j])
-#pragma unroll
-                for (int c = 0; c < NC; ++c) __builtin_nontemporal_store(v[j][c], &cols.dst[c][base + j * 64]);
-        lds_barrier();
-        if (t < kPsDig) run[t] += tot_s[t];
-    }
-}
-
-// Filter + partition ids + per-segment histogram in one pass (config 4's probe side, fewer than
-// kPsDig partitions): block b streams its segment [b * seg, (b + 1) * seg) -- seg a multiple of the
-// 8192-row tile -- with FastTile's 16-B loads of the key and up to two term columns (every load of a
-// tile issued before the predicate), writes the ids as u16 pairs and counts them per partition in
-// byte-packed register counters, so no histogram pass re-reads the id stream.  The generic id pass
-// (k_hash_ids8_pred) evaluated the predicate and loaded the key in two dependent rounds of 4-row
-// loads (3.1 TB/s).  Rows past the last whole tile (the tail of the last segment) go row by row.
-__device__ __forceinline__ uint32_t part_of_key(int64_t k, uint32_t parts) {
-    uint64_t h = 0x9E3779B97F4A7C15ull;  // k_hash_ids8's hash of one non-null key column
-    h = hash64(h ^ (hash64((uint64_t)k) + 0x9E3779B97F4A7C15ull + (h << 6) + (h >> 2)));
-    return (uint32_t)(h % parts);
-}
-
-template <int NTERMS>
-__global__ __launch_bounds__(kRsThreads) void k_ids_hist_pred(FastIn in, PredTerms terms, int64_t n, int64_t seg,
-                                                              uint32_t parts, uint8_t *__restrict__ ids,
-                                                              uint32_t *__restrict__ hist, int nblocks) {
-    constexpr int W = kRsThreads / 64, TILE = kRsThreads * kFastR;
-    __shared__ uint32_t wc[W][kPsDig];
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int64_t lo = (int64_t)blockIdx.x * seg, hi = lo + seg < n ? lo + seg : n;
-    const int64_t full = hi > lo ? lo + (hi - lo) / TILE * TILE : lo;
-    uint32_t cnt[kPsDig];
-#pragma unroll
-    for (int d = 0; d < kPsDig; ++d) cnt[d] = 0u;
-    uint64_t acc[2] = {0ull, 0ull};  // byte counters of partitions 0-7 / 8-15 (flushed before 256)
-    auto flush = [&]() {
-#pragma unroll
-        for (int d = 0; d < kPsDig; ++d) cnt[d] += (uint32_t)(acc[d >> 3] >> (8 * (d & 7))) & 0xFFu;
-        acc[0] = acc[1] = 0ull;
-    };
-    FastTile<NTERMS, 0, true> ft;
-    int tiles = 0;
-    if (lo < full) ft.issue(in, lo + (int64_t)wave * 512 + 2 * lane);
-    for (int64_t t0 = lo; t0 < full; t0 += TILE) {
-        ft.eval(in, terms);
-        uint32_t id[kFastR];
-#pragma unroll
-        for (int r = 0; r < kFastR; ++r) id[r] = ((ft.sel >> r) & 1u) ? part_of_key(ft.k(r), parts) : parts;
-        if (t0 + TILE < full) ft.issue(in, t0 + TILE + (int64_t)wave * 512 + 2 * lane);
-        const int64_t base = t0 + (int64_t)wave * 512 + 2 * lane;
-#pragma unroll
-        for (int j = 0; j < kFastPairs; ++j) {
-            *(uint16_t *)(ids + base + j * 128) = (uint16_t)(id[2 * j] | (id[2 * j + 1] << 8));
-#pragma unroll
-            for (int q = 0; q < 2; ++q) {
-                const uint32_t d = id[2 * j + q];
-                const uint64_t one = 1ull << (8 * (d & 7));
-                acc[0] += d < 8 ? one : 0ull;
-                acc[1] += d < 8 ? 0ull : one;
-            }
-        }
-        if (++tiles == 31) {  // 31 tiles x 8 rows < 256 per byte counter
-            flush();
-            tiles = 0;
-        }
-    }
-    flush();
-    for (int64_t i = full + t; i < hi; i += kRsThreads) {  // ragged tail, one row per thread
-        bool ok = NTERMS == 0 || !terms.is_or;
-#pragma unroll
-        for (int q = 0; q < NTERMS; ++q) {
-            const PredTerm pt = terms.t[q];
-            int64_t v = in.term[q][i];
-            if (pt.ctype == QEH_DT_FLOAT64) v = f64_order_key(in.term_dt[q] == QEH_DT_FLOAT64 ? as_f64(v) : (double)v);
-            const bool tr = cmp_i64(pt.op, v, pt.lit);
-            ok = terms.is_or ? (q == 0 ? tr : (ok || tr)) : (ok && tr);
-        }
-        const uint32_t d = ok ? part_of_key(in.key[i], parts) : parts;
-        ids[i] = (uint8_t)d;
-#pragma unroll
-        for (int e = 0; e < kPsDig; ++e) cnt[e] += d == (uint32_t)e ? 1u : 0u;
-    }
-#pragma unroll
-    for (int d = 0; d < kPsDig; ++d) {
-        uint32_t c = cnt[d];
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) c += __shfl_xor(c, o, 64);
-        if (lane == 0) wc[wave][d] = c;
-    }
-    __syncthreads();
-    if (t < kPsDig) {
-        uint32_t c = 0;
-#pragma unroll
-        for (int w = 0; w < W; ++w) c += wc[w][t];
-        hist[(int64_t)t * nblocks + blockIdx.x] = c;  // digit-major, as k_rs_hist_u8
-    }
-}
-
-// Sort state: encoded keys + permutation, double-buffered.
-struct RadixState {
-    DevBuf k[2], v[2];
-    int cur = 0;
-    int64_t n = 0;
-    bool enc_injective = false;  // k[cur] encodes the last-sorted column one-to-one (no null-flag pass)
-    int part_shift = -1;         // >= 0: k[cur] holds (first key << part_shift) | ..., the pair encoding
-    bool key32 = false;          // k[] currently holds 32-bit keys (column range fits 32 bits)
-};
-
-// ballot ranking when asked for (QEH_RS_BALLOT=1, A/B) or when the device's LDS atomics failed the
-// lane-order self-check (lds_atomic_rank_ok)
-static bool rs_ballot(qeh_ctx *ctx) {
-    return std::getenv("QEH_RS_BALLOT") != nullptr || !lds_atomic_rank_ok(ctx);
-}
-
-// Stable LSD passes over the low `bits` of the encoded keys in rs.
-template <typename KeyT>
-static int radix_passes_t(qeh_ctx *ctx, RadixState &rs, int bits) {
-    const int64_t n = rs.n;
-    if (n <= 1 || bits <= 0) return QEH_OK;
-    // one long-lived scatter workgroup per CU (see k_rs_scatter); hist uses the same segments
-    const int nblocks = (int)std::min<int64_t>(std::max<int64_t>((n + kRsSTile - 1) / kRsSTile, 1), (int64_t)ctx->props.multiProcessorCount);
-    const int64_t seg = (n + nblocks - 1) / nblocks;
-    DevBuf hist, offs, nd;
-    QEH_TRY(hist.alloc(ctx, (size_t)kRadix * nblocks * 4));
-    QEH_TRY(offs.alloc(ctx, (size_t)kRadix * nblocks * 8));
-    // every scatter but the last also writes the next pass's digit as one byte per element, so
-    // that pass's histogram reads 1 B instead of the key (sizeof(KeyT) B)
-    const bool multi = bits > kRadixBits && n >= (int64_t)kRsSTile;
-    if (multi) QEH_TRY(nd.alloc(ctx, (size_t)n));
-    for (int shift = 0; shift < bits; shift += kRadixBits) {
-        KernelTimer kt(ctx, "radix_pass");
-        const int c = rs.cur;
-        if (multi && shift > 0)
-            hipLaunchKernelGGL(k_rs_hist_u8, dim3(nblocks), dim3(kRsThreads), 0, ctx->stream, nd.as<uint8_t>(), n, seg,
-                               hist.as<uint32_t>(), nblocks);
-        else
-            hipLaunchKernelGGL(k_rs_hist<KeyT>, dim3(nblocks), dim3(kRsThreads), 0, ctx->stream, rs.k[c].as<KeyT>(), n, seg,
-                               shift, hist.as<uint32_t>(), nblocks, RsEncode{});
-        QEH_HIP(hipGetLastError());
-        QEH_TRY(exclusive_scan_u32(ctx, hist.as<uint32_t>(), offs.as<uint64_t>(), (int64_t)kRadix * nblocks, nullptr));
-        const bool next = multi && shift + kRadixBits < bits;
-        auto scat = rs_ballot(ctx) ? k_rs_scatter<KeyT, false> : k_rs_scatter<KeyT, true>;
-        hipLaunchKernelGGL(scat, dim3(nblocks), dim3(kRsThreads), 0, ctx->stream, rs.k[c].as<KeyT>(), rs.v[c].as<uint32_t>(), n, seg, shift, offs.as<uint64_t>(),
-                           nblocks, rs.k[1 - c].as<KeyT>(), rs.v[1 - c].as<uint32_t>(), next ? nd.as<uint8_t>() : nullptr,
-                           shift + kRadixBits, RsDecode{}, RsEncode{}, nullptr);
-        QEH_HIP(hipGetLastError());
-        rs.cur = 1 - c;
-    }
-    return QEH_OK;
-}
-
-// One stable pass on the 8-bit digit at `shift` (u32 / u64 keys as KeyT).
-template <typename KeyT>
-static int radix_pass_at(qeh_ctx *ctx, RadixState &rs, int shift) {
-    const int64_t n = rs.n;
-    if (n <= 1) return QEH_OK;
-    const int nblocks = (int)std::min<int64_t>(std::max<int64_t>((n + kRsSTile - 1) / kRsSTile, 1), (int64_t)ctx->props.multiProcessorCount);
-    const int64_t seg = (n + nblocks - 1) / nblocks;
+// The grid of the LSD passes over n rows and their histogram / offset buffers: one long-lived scatter
+// workgroup per CU (see k_rs_scatter); hist uses the same segments.
+struct RadixGrid {
+    int nblocks = 0;
+    int64_t seg = 0;
     DevBuf hist, offs;
-    QEH_TRY(hist.alloc(ctx, (size_t)kRadix * nblocks * 4));
-    QEH_TRY(offs.alloc(ctx, (size_t)kRadix * nblocks * 8));
+    int init(qeh_ctx *ctx, int64_t n) {
+        nblocks = (int)std::min<int64_t>(std::max<int64_t>((n + kRsSTile - 1) / kRsSTile, 1), (int64_t)ctx->props.multiProcessorCount);
+        seg = (n + nblocks - 1) / nblocks;
+        QEH_TRY(hist.alloc(ctx, (size_t)kRadix * nblocks * 4));
+        return offs.alloc(ctx, (size_t)kRadix * nblocks * 8);
+    }
+};
+
+// One stable pass on the 8-bit digit at `shift` (u32 / u64 keys as KeyT).  nd_in: the digits as the
+// byte stream the previous scatter wrote (else read from the keys); nd_out: where this scatter
+// writes the digits at `nshift` for the next pass (else nullptr).
+template <typename KeyT>
+static int radix_pass_t(qeh_ctx *ctx, RadixState &rs, RadixGrid &g, int shift, const uint8_t *nd_in, uint8_t *nd_out,
+                        int nshift) {
     KernelTimer kt(ctx, "radix_pass");
+    const int64_t n = rs.n;
     const int c = rs.cur;
-    hipLaunchKernelGGL(k_rs_hist<KeyT>, dim3(nblocks), dim3(kRsThreads), 0, ctx->stream, rs.k[c].as<KeyT>(), n, seg, shift,
-                       hist.as<uint32_t>(), nblocks, RsEncode{});
+    if (nd_in)
+        launch_hist_u8(ctx, nd_in, n, g.seg, g.hist.as<uint32_t>(), g.nblocks);
+    else
+        hipLaunchKernelGGL(k_rs_hist<KeyT>, dim3(g.nblocks), dim3(kRsThreads), 0, ctx->stream, rs.k[c].as<KeyT>(), n, g.seg,
+                           shift, g.hist.as<uint32_t>(), g.nblocks, RsEncode{});
     QEH_HIP(hipGetLastError());
-    QEH_TRY(exclusive_scan_u32(ctx, hist.as<uint32_t>(), offs.as<uint64_t>(), (int64_t)kRadix * nblocks, nullptr));
+    QEH_TRY(exclusive_scan_u32(ctx, g.hist.as<uint32_t>(), g.offs.as<uint64_t>(), (int64_t)kRadix * g.nblocks, nullptr));
     auto scat = rs_ballot(ctx) ? k_rs_scatter<KeyT, false> : k_rs_scatter<KeyT, true>;
-    hipLaunchKernelGGL(scat, dim3(nblocks), dim3(kRsThreads), 0, ctx->stream, rs.k[c].as<KeyT>(), rs.v[c].as<uint32_t>(), n, seg, shift, offs.as<uint64_t>(), nblocks,
-                       rs.k[1 - c].as<KeyT>(), rs.v[1 - c].as<uint32_t>(), nullptr, 0, RsDecode{}, RsEncode{}, nullptr);
+    hipLaunchKernelGGL(scat, dim3(g.nblocks), dim3(kRsThreads), 0, ctx->stream, rs.k[c].as<KeyT>(), rs.v[c].as<uint32_t>(), n,
+                       g.seg, shift, g.offs.as<uint64_t>(), g.nblocks, rs.k[1 - c].as<KeyT>(), rs.v[1 - c].as<uint32_t>(),
+                       nd_out, nshift, RsDecode{}, RsEncode{}, nullptr);
     QEH_HIP(hipGetLastError());
     rs.cur = 1 - c;
     return QEH_OK;
 }
 
-static int gc_of(qeh_ctx *ctx, int64_t nchunks) {
-    return (int)std::min<int64_t>(nchunks, (int64_t)ctx->props.multiProcessorCount * 8);
+static int radix_pass(qeh_ctx *ctx, RadixState &rs, RadixGrid &g, int shift, const uint8_t *nd_in, uint8_t *nd_out,
+                      int nshift) {
+    return rs.key32 ? radix_pass_t<uint32_t>(ctx, rs, g, shift, nd_in, nd_out, nshift)
+                    : radix_pass_t<uint64_t>(ctx, rs, g, shift, nd_in, nd_out, nshift);
 }
 
-// Stable LSD passes over the low `bits` of the encoded keys in rs.
-static int radix_passes(qeh_ctx *ctx, RadixState &rs, int bits) {
-    return rs.key32 ? radix_passes_t<uint32_t>(ctx, rs, bits) : radix_passes_t<uint64_t>(ctx, rs, bits);
+int radix_passes(qeh_ctx *ctx, RadixState &rs, int bits) {
+    const int64_t n = rs.n;
+    if (n <= 1 || bits <= 0) return QEH_OK;
+    RadixGrid g;
+    QEH_TRY(g.init(ctx, n));
+    // every scatter but the last also writes the next pass's digit as one byte per element, so
+    // that pass's histogram reads 1 B instead of the key (4 or 8 B)
+    DevBuf nd;
+    const bool multi = bits > kRadixBits && n >= (int64_t)kRsSTile;
+    if (multi) QEH_TRY(nd.alloc(ctx, (size_t)n));
+    for (int shift = 0; shift < bits; shift += kRadixBits) {
+        const bool next = multi && shift + kRadixBits < bits;
+        QEH_TRY(radix_pass(ctx, rs, g, shift, multi && shift > 0 ? nd.as<uint8_t>() : nullptr,
+                           next ? nd.as<uint8_t>() : nullptr, shift + kRadixBits));
+    }
+    return QEH_OK;
 }
 
-static int bit_length(uint64_t x) {
-    int b = 0;
-    while (b < 64 && (x >> b) != 0) ++b;
-    return b;
+int radix_pass_at(qeh_ctx *ctx, RadixState &rs, int shift) {
+    if (rs.n <= 1) return QEH_OK;
+    RadixGrid g;
+    QEH_TRY(g.init(ctx, rs.n));
+    return radix_pass(ctx, rs, g, shift, nullptr, nullptr, 0);
 }
 
 // Encode key column `c` through the current permutation (or identity) and
@@ -1050,19 +621,10 @@ static int bit_length(uint64_t x) {
 static int sort_by_column(qeh_ctx *ctx, RadixState &rs, const qeh_column &col, bool asc, bool first,
                           bool nulls_last = false) {
     const ColRef c = make_colref(col);
-    const int64_t n = rs.n;
-    DevBuf st;
-    QEH_TRY(st.alloc(ctx, sizeof(KeyStats)));
+    const int64_t n = rs.n;  // == col.length (check_sort_keys)
+    // min/max do not depend on row order: read the column directly, not through the permutation
     KeyStats ks{};
-    {
-        KernelTimer kt(ctx, "sort_encode");
-        hipLaunchKernelGGL(k_stats_init, dim3(1), dim3(1), 0, ctx->stream, st.as<KeyStats>());
-        // min/max do not depend on row order: read the column directly, not through the permutation
-        hipLaunchKernelGGL(k_key_stats, dim3(grid_for(ctx, n, kBlock * 8, 1)), dim3(kBlock), 0, ctx->stream, c, nullptr, n,
-                           st.as<KeyStats>());
-    }
-    QEH_HIP(hipGetLastError());
-    QEH_TRY(read_small(ctx, &ks, st.p, sizeof ks));
+    QEH_TRY(sort_key_range(ctx, col, &ks.mn, &ks.mx));
     const bool nullable = col.validity != nullptr && col.null_count != 0;
     int bits = 1;  // all NULL (or empty)
     // NULLs first: NULL -> 0, values -> 1 .. span+1; NULLs last: values -> 0 .. span, NULL -> span+1
@@ -1236,8 +798,8 @@ static int sort_perm_pair(qeh_ctx *ctx, const qeh_column &ca, const qeh_column &
 }
 
 // Stable lexicographic permutation by keys (last key sorted first).
-static int sort_perm(qeh_ctx *ctx, const qeh_column *keys, int n_keys, const int8_t *ascending, int64_t n,
-                     RadixState &rs, const int8_t *nulls_first = nullptr) {
+int sort_perm(qeh_ctx *ctx, const qeh_column *keys, int n_keys, const int8_t *ascending, int64_t n, RadixState &rs,
+              const int8_t *nulls_first) {
     rs.n = n;
     for (int b = 0; b < 2; ++b) {
         QEH_TRY(rs.k[b].alloc(ctx, (size_t)std::max<int64_t>(n, 1) * 8));
@@ -1259,7 +821,7 @@ static int sort_perm(qeh_ctx *ctx, const qeh_column *keys, int n_keys, const int
     return QEH_OK;
 }
 
-static int check_sort_keys(const qeh_column *keys, int n_keys, int64_t *n) {
+int check_sort_keys(const qeh_column *keys, int n_keys, int64_t *n) {
     if (n_keys < 1) return fail(QEH_E_INVALID, "sort needs at least one key");
     *n = keys[0].length;
     for (int j = 0; j < n_keys; ++j) {
@@ -1271,359 +833,10 @@ static int check_sort_keys(const qeh_column *keys, int n_keys, int64_t *n) {
     return QEH_OK;
 }
 
-// ---- ROW_NUMBER ----------------------------------------------------------------------------
-// flags[i] = 1 when sorted row i starts a new partition (partition columns differ from row i-1)
-// One gather per row: each lane loads its row's keys through the permutation and takes the
-// previous row's from the lane below (lane 0 loads its predecessor itself), halving the random
-// reads of comparing perm[i-1] with perm[i] directly.  Whole workgroups step together, so every
-// lane of a wave reaches the shuffles.
-__global__ void k_part_flags(KeyCols part, const uint32_t *__restrict__ perm, int64_t n, uint32_t *__restrict__ flags) {
-    const int lane = threadIdx.x & 63;
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t base = (int64_t)blockIdx.x * blockDim.x; base < n; base += stride) {
-        const int64_t i = base + threadIdx.x;
-        const bool act = i < n;
-        const int64_t b = act ? (int64_t)perm[i] : 0;
-        const bool own_prev = act && lane == 0 && i > 0;
-        const int64_t a = own_prev ? (int64_t)perm[i - 1] : 0;
-        uint32_t f = 0;
-        for (int c = 0; c < part.n; ++c) {
-            const int vb = act && col_valid(part.c[c], b) ? 1 : 0;
-            const int64_t xb = vb ? load_i64(part.c[c], b) : 0;
-            int va = __shfl_up(vb, 1, 64);
-            int64_t xa = __shfl_up(xb, 1, 64);
-            if (own_prev) {
-                va = col_valid(part.c[c], a) ? 1 : 0;
-                xa = va ? load_i64(part.c[c], a) : 0;
-            }
-            if (va != vb || (va && xa != xb)) f = 1;
-        }
-        if (act) flags[i] = i == 0 ? 1u : f;
-    }
-}
-
-// single partition key: compare the sorted encodings (coalesced) instead of
-// gathering the key column through the permutation.  shift >= the key width means the
-// partition key occupies no bits (one distinct value): only row 0 starts a partition (a shift
-// by the full width would be undefined and the hardware masks it to 0).
-template <typename KeyT>
-__global__ void k_part_flags_enc(const KeyT *__restrict__ enc, int64_t n, uint32_t *__restrict__ flags, int shift = 0) {
-    const bool one_part = shift >= (int)(8 * sizeof(KeyT));
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-        flags[i] = i == 0 || (!one_part && (enc[i] >> shift) != (enc[i - 1] >> shift));
-}
-
-// Row numbers without materialising partition ids: rn(i) = i - start(i) + 1,
-// start(i) = the last partition start <= i.  Chunks of kRnChunk sorted
-// positions: (1) each chunk's last start, (2) an exclusive prefix max over
-// chunks, (3) per chunk a block max-scan seeded with (2), then the scatter
-// rn[perm[i]] into input order.  No partition count is read back.
-constexpr int kRnPer = 16;
-constexpr int64_t kRnChunk = (int64_t)kBlock * kRnPer;
-
-__global__ __launch_bounds__(kBlock) void k_rn_chunk_last(const uint32_t *__restrict__ flags, int64_t n, int64_t nchunks,
-                                                          int64_t *__restrict__ last) {
-    __shared__ int64_t red[kBlock / 64];
-    for (int64_t c = blockIdx.x; c < nchunks; c += gridDim.x) {
-        int64_t m = -1;
-        const int64_t base = c * kRnChunk;
-        for (int j = 0; j < kRnPer; ++j) {
-            const int64_t i = base + (int64_t)j * kBlock + threadIdx.x;
-            if (i < n && flags[i]) m = i > m ? i : m;
-        }
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) {
-            const int64_t o = __shfl_xor(m, d, 64);
-            m = o > m ? o : m;
-        }
-        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            for (int w = 1; w < kBlock / 64; ++w) m = red[w] > m ? red[w] : m;
-            last[c] = m;
-        }
-        __syncthreads();
-    }
-}
-
-// in place: last[c] <- max(last[0..c-1]) (exclusive), one workgroup
-__global__ __launch_bounds__(1024) void k_rn_prefix_max(int64_t *__restrict__ last, int64_t nchunks) {
-    __shared__ int64_t part[1024];
-    const int t = threadIdx.x;
-    const int64_t per = (nchunks + 1023) / 1024, lo = (int64_t)t * per, hi = lo + per < nchunks ? lo + per : nchunks;
-    int64_t m = -1;
-    for (int64_t c = lo; c < hi; ++c) m = last[c] > m ? last[c] : m;
-    part[t] = m;
-    __syncthreads();
-    if (t == 0) {
-        int64_t run = -1;
-        for (int i = 0; i < 1024; ++i) {
-            const int64_t x = part[i];
-            part[i] = run;
-            run = x > run ? x : run;
-        }
-    }
-    __syncthreads();
-    int64_t run = part[t];
-    for (int64_t c = lo; c < hi; ++c) {
-        const int64_t x = last[c];
-        last[c] = run;
-        run = x > run ? x : run;
-    }
-}
-
-// PAIRS: instead of scattering rn[perm[i]] (1e9 random 8-byte writes), write the pairs
-// (perm[i], rn) in sorted order; one stable radix pass on the destination's top bits then
-// groups them by output window and k_rn_scatter_windows writes one window at a time
-template <bool PAIRS>
-__global__ __launch_bounds__(kBlock) void k_rn_write(const uint32_t *__restrict__ flags, const int64_t *__restrict__ carry,
-                                                     const uint32_t *__restrict__ perm, int64_t n, int64_t nchunks,
-                                                     int64_t *__restrict__ rn, uint32_t *__restrict__ pair_dst,
-                                                     uint32_t *__restrict__ pair_rn) {
-    __shared__ int64_t wmax[kBlock / 64];
-    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
-    for (int64_t c = blockIdx.x; c < nchunks; c += gridDim.x) {
-        // thread t owns kRnPer consecutive positions
-        const int64_t base = c * kRnChunk + (int64_t)t * kRnPer;
-        uint32_t f[kRnPer];
-        int64_t m = -1;
-#pragma unroll
-        for (int j = 0; j < kRnPer; ++j) {
-            const int64_t i = base + j;
-            f[j] = i < n ? flags[i] : 0u;
-            if (f[j]) m = i;
-        }
-        // exclusive max-scan of the threads' last starts, seeded with the chunks before
-        int64_t incl = m;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const int64_t o = __shfl_up(incl, d, 64);
-            if (lane >= d) incl = o > incl ? o : incl;
-        }
-        if (lane == 63) wmax[w] = incl;
-        __syncthreads();
-        int64_t start = carry[c];
-        for (int q = 0; q < w; ++q) start = wmax[q] > start ? wmax[q] : start;
-        const int64_t prev = __shfl_up(incl, 1, 64);
-        if (lane > 0) start = prev > start ? prev : start;
-#pragma unroll
-        for (int j = 0; j < kRnPer; ++j) {
-            const int64_t i = base + j;
-            if (f[j]) start = i;
-            if (i < n) {
-                if (PAIRS) {
-                    pair_dst[i] = perm[i];
-                    pair_rn[i] = (uint32_t)(i - start + 1);
-                } else {
-                    rn[perm[i]] = i - start + 1;
-                }
-            }
-        }
-        __syncthreads();
-    }
-}
-
-// pairs grouped by output window (destination >> shift): consecutive workgroups write inside
-// one window at a time, so the partial-line writes meet in L2 / the Infinity Cache instead of HBM
-__global__ void k_rn_scatter_windows(const uint32_t *__restrict__ dst, const uint32_t *__restrict__ val, int64_t n,
-                                     int64_t *__restrict__ out) {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-        out[dst[i]] = (int64_t)val[i];
-}
-
-// start of every window in the window-grouped pairs (empty windows start where the next begins)
-__global__ void k_rn_window_starts(const uint32_t *__restrict__ dst, int64_t n, int shift, int64_t nwin,
-                                   int64_t *__restrict__ start) {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i <= n; i += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t w = i < n ? (int64_t)(dst[i] >> shift) : nwin;
-        const int64_t wp = i > 0 ? (int64_t)(dst[i - 1] >> shift) : -1;
-        for (int64_t q = wp + 1; q <= w; ++q) start[q] = i;  // windows (wp, w] begin at i
-    }
-}
-
-// XCD-local windows: workgroup b runs on XCD b % 8 (round-robin dispatch), and the workgroups of
-// one XCD walk that XCD's windows (w = xcd, xcd + 8, ...) together, so a window's output lines
-// (2 MB) are completed inside one L2 before they are written back
-__global__ void k_rn_scatter_xcd(const uint32_t *__restrict__ dst, const uint32_t *__restrict__ val,
-                                 const int64_t *__restrict__ start, int64_t nwin, int64_t *__restrict__ out) {
-    constexpr int kXcd = 8;
-    const int xcd = blockIdx.x % kXcd;
-    const int64_t per = gridDim.x / kXcd, me = blockIdx.x / kXcd;
-    for (int64_t w = xcd; w < nwin; w += kXcd) {
-        const int64_t a = start[w], b = start[w + 1];
-        for (int64_t i = a + me * blockDim.x + threadIdx.x; i < b; i += per * blockDim.x) out[dst[i]] = (int64_t)val[i];
-    }
-}
-
-// ---- hash partition ---------------------------------------------------------------------------
-__global__ void k_partition_ids(ColRef key, int64_t n, uint32_t parts, uint64_t *__restrict__ keys,
-                                uint32_t *__restrict__ idx) {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        uint32_t p = 0;  // NULL keys hash like an empty key (partition.rs:292-316 skips them)
-        if (col_valid(key, i)) p = (uint32_t)(hash64((uint64_t)load_i64(key, i)) % parts);
-        keys[i] = p;
-        idx[i] = (uint32_t)i;
-    }
-}
-
-// range partition: NULL -> 0 (NULLs sort first); value -> number of splitters
-// strictly below (ascending) / above (descending) its order key, so equal keys
-// share a partition and partition p precedes p+1 in sort order
-__global__ void k_range_ids(ColRef key, int64_t n, const int64_t *__restrict__ split, int n_split, int asc,
-                            uint64_t *__restrict__ keys, uint32_t *__restrict__ idx) {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        uint32_t p = 0;
-        if (col_valid(key, i)) {
-            const int64_t k = ordered_key(key, i);
-            for (int j = 0; j < n_split; ++j) p += asc ? split[j] < k : split[j] > k;
-        }
-        keys[i] = p;
-        idx[i] = (uint32_t)i;
-    }
-}
-
-// PartitionStrategy::Hash over several key columns (partition.rs:151-212, compute_row_hash
-// :292-316): NULL cells contribute nothing to the row hash, as the reference skips them; Int32 /
-// Int64 values and Utf8 bytes are mixed into one 64-bit hash (the hash function is not
-// observable in results).
-struct HashKeys {
-    ColRef c[kMaxCols];
-    const int32_t *offs[kMaxCols];
-    const uint8_t *data[kMaxCols];
-    int32_t n;
-};
-
-__global__ void k_hash_ids_multi(HashKeys keys, int64_t n, uint32_t parts, uint64_t *__restrict__ ids,
-                                 uint32_t *__restrict__ idx) {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        uint64_t h = 0x9E3779B97F4A7C15ull;
-        for (int j = 0; j < keys.n; ++j) {
-            const ColRef &c = keys.c[j];
-            if (!col_valid(c, i)) continue;
-            uint64_t v;
-            if (c.dtype == QEH_DT_UTF8) {
-                v = 0xcbf29ce484222325ull;  // FNV-1a over the bytes
-                for (int32_t b = keys.offs[j][i]; b < keys.offs[j][i + 1]; ++b) v = (v ^ keys.data[j][b]) * 0x100000001b3ull;
-            } else {
-                v = (uint64_t)load_i64(c, i);
-            }
-            h = hash64(h ^ (hash64(v) + 0x9E3779B97F4A7C15ull + (h << 6) + (h >> 2)));
-        }
-        ids[i] = h % parts;
-        idx[i] = (uint32_t)i;
-    }
-}
-
-__global__ void k_hash_ids8(HashKeys keys, int64_t n, uint32_t parts, uint8_t *__restrict__ ids) {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        uint64_t h = 0x9E3779B97F4A7C15ull;
-        for (int j = 0; j < keys.n; ++j) {
-            const ColRef &c = keys.c[j];
-            if (!col_valid(c, i)) continue;
-            uint64_t v;
-            if (c.dtype == QEH_DT_UTF8) {
-                v = 0xcbf29ce484222325ull;
-                for (int32_t b = keys.offs[j][i]; b < keys.offs[j][i + 1]; ++b) v = (v ^ keys.data[j][b]) * 0x100000001b3ull;
-            } else {
-                v = (uint64_t)load_i64(c, i);
-            }
-            h = hash64(h ^ (hash64(v) + 0x9E3779B97F4A7C15ull + (h << 6) + (h >> 2)));
-        }
-        ids[i] = (uint8_t)(h % parts);
-    }
-}
-
-// k_hash_ids8 for one non-null Int64 key column: eight rows per thread (four 16-B loads, one 8-B
-// store of ids), the same hash.
-__global__ __launch_bounds__(kBlock) void k_hash_ids8_i64(const int64_t *__restrict__ key, int64_t n, uint32_t parts,
-                                                          uint8_t *__restrict__ ids) {
-    typedef long long v2i64h __attribute__((ext_vector_type(2)));
-    for (int64_t i0 = ((int64_t)blockIdx.x * kBlock + threadIdx.x) * 8; i0 < n; i0 += (int64_t)gridDim.x * kBlock * 8) {
-        uint64_t v[8];
-        if (i0 + 8 <= n && (((uintptr_t)(key + i0)) & 15) == 0) {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const v2i64h w = __builtin_nontemporal_load((const v2i64h *)(key + i0) + q);
-                v[2 * q] = (uint64_t)w[0], v[2 * q + 1] = (uint64_t)w[1];
-            }
-        } else {
-#pragma unroll
-            for (int q = 0; q < 8; ++q) v[q] = i0 + q < n ? (uint64_t)key[i0 + q] : 0ull;
-        }
-        uint64_t out = 0;
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {
-            uint64_t h = 0x9E3779B97F4A7C15ull;
-            h = hash64(h ^ (hash64(v[q]) + 0x9E3779B97F4A7C15ull + (h << 6) + (h >> 2)));
-            out |= (uint64_t)(uint8_t)(h % parts) << (8 * q);
-        }
-        if (i0 + 8 <= n) {
-            *(uint64_t *)(ids + i0) = out;
-        } else {
-            for (int q = 0; q < 8 && i0 + q < n; ++q) ids[i0 + q] = (uint8_t)(out >> (8 * q));
-        }
-    }
-}
-
-// The filter of a shuffle fused into the Exchange's id pass (config 4's probe side): rows whose
-// predicate (an AND / OR list of column-literal comparisons) is TRUE get hash(key) % parts,
-// the others `parts` (dropped by k_part_scatter).  One key column, Int32 / Int64.
-__global__ __launch_bounds__(kBlock) void k_hash_ids8_pred(ColRef key, ColSet cols, PredTerms terms, int64_t n,
-                                                           uint32_t parts, uint8_t *__restrict__ ids) {
-    constexpr int R = 4;
-    for (int64_t t0 = (int64_t)blockIdx.x * kBlock * R; t0 < n; t0 += (int64_t)gridDim.x * kBlock * R) {
-        const int64_t row0 = t0 + threadIdx.x;
-        const uint32_t m = eval_terms<R>(terms, cols, row0, kBlock, n);
-        int64_t kv[R];
-        uint32_t kvalid;
-        load_rows<R>(key, row0, kBlock, n, kv, kvalid);
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-            const int64_t i = row0 + (int64_t)r * kBlock;
-            if (i >= n) continue;
-            uint64_t h = 0x9E3779B97F4A7C15ull;  // k_hash_ids8's hash of one key column (NULL skipped)
-            if ((kvalid >> r) & 1u) h = hash64(h ^ (hash64((uint64_t)kv[r]) + 0x9E3779B97F4A7C15ull + (h << 6) + (h >> 2)));
-            ids[i] = ((m >> r) & 1u) ? (uint8_t)(h % parts) : (uint8_t)parts;
-        }
-    }
-}
-
-// PartitionStrategy::Range (find_range_partition, partition.rs:320-341): the first boundary the
-// value is below, or len(boundaries); NULL -> 0; only Int64 keys are ranged (every other column
-// type lands in partition 0, as in the reference)
-__global__ void k_range_ids_first_below(ColRef key, int64_t n, const int64_t *__restrict__ b, int nb, int is_i64,
-                                        uint64_t *__restrict__ ids, uint32_t *__restrict__ idx) {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        uint32_t p = 0;
-        if (is_i64 && col_valid(key, i)) {
-            const int64_t v = ((const int64_t *)key.values)[i];
-            p = (uint32_t)nb;
-            for (int j = 0; j < nb; ++j)
-                if (v < b[j]) {
-                    p = (uint32_t)j;
-                    break;
-                }
-        }
-        ids[i] = p;
-        idx[i] = (uint32_t)i;
-    }
-}
-
 template <typename T>
 __global__ void k_scatter(const T *__restrict__ src, const uint32_t *__restrict__ idx, int64_t m, T *__restrict__ out) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < m; i += (int64_t)gridDim.x * blockDim.x)
         out[idx[i]] = src[i];
-}
-
-__global__ void k_count_parts(const uint64_t *__restrict__ ids, int64_t n, int parts, unsigned long long *__restrict__ counts) {
-    __shared__ uint32_t h[kRadix];
-    for (int i = threadIdx.x; i < kRadix; i += blockDim.x) h[i] = 0;
-    __syncthreads();
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-        atomicAdd(&h[ids[i]], 1u);
-    __syncthreads();
-    for (int p = threadIdx.x; p < parts; p += blockDim.x)
-        if (h[p]) atomicAdd(&counts[p], (unsigned long long)h[p]);
 }
 
 __global__ void k_u64_to_u32_idx(const int64_t *__restrict__ in, int64_t n, int64_t limit, uint32_t *__restrict__ out,
@@ -1641,8 +854,6 @@ __global__ void k_perm_prefix(const uint32_t *__restrict__ perm, const uint32_t 
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < m; i += (int64_t)gridDim.x * blockDim.x)
         out[i] = rows ? rows[perm[i]] : perm[i];
 }
-
-int sort_check_keys(const qeh_column *keys, int n_keys, int64_t *n) { return check_sort_keys(keys, n_keys, n); }
 
 int sort_key_range(qeh_ctx *ctx, const qeh_column &col, int64_t *mn, int64_t *mx) {
     DevBuf st;
@@ -1679,23 +890,35 @@ int sort_perm_prefix(qeh_ctx *ctx, const qeh_column *keys, int n_keys, const int
 
 using namespace qeh;
 
-extern "C" int qeh_sort_indices(qeh_ctx *ctx, const qeh_column *keys, int n_keys, const int8_t *ascending,
-                                qeh_column *out_perm) {
-    if (!ctx || !keys || !out_perm) return fail(QEH_E_INVALID, "qeh_sort_indices: bad argument");
+// qeh_sort_indices / qeh_sort_indices_nulls (nulls_first == nullptr: NULLs first for every key)
+static int sort_indices(qeh_ctx *ctx, const qeh_column *keys, int n_keys, const int8_t *ascending, const int8_t *nulls_first,
+                        qeh_column *out_perm) {
     DeviceGuard dg(ctx->device);
     if (any_utf8(keys, n_keys)) {  // codes compare as the strings do
         Utf8Keys uk;
         QEH_TRY(encode_utf8_keys(ctx, keys, n_keys, &uk));
-        return qeh_sort_indices(ctx, uk.keys.data(), n_keys, ascending, out_perm);
+        return sort_indices(ctx, uk.keys.data(), n_keys, ascending, nulls_first, out_perm);
     }
     int64_t n;
     QEH_TRY(check_sort_keys(keys, n_keys, &n));
     RadixState rs;
-    QEH_TRY(sort_perm(ctx, keys, n_keys, ascending, n, rs));
+    QEH_TRY(sort_perm(ctx, keys, n_keys, ascending, n, rs, nulls_first));
     QEH_TRY(alloc_column(ctx, QEH_DT_UINT32, n, false, out_perm));
     if (n > 0) QEH_HIP(hipMemcpyAsync(out_perm->values, rs.v[rs.cur].p, (size_t)n * 4, hipMemcpyDeviceToDevice, ctx->stream));
     QEH_HIP(hipStreamSynchronize(ctx->stream));
     return QEH_OK;
+}
+
+extern "C" int qeh_sort_indices(qeh_ctx *ctx, const qeh_column *keys, int n_keys, const int8_t *ascending,
+                                qeh_column *out_perm) {
+    if (!ctx || !keys || !out_perm) return fail(QEH_E_INVALID, "qeh_sort_indices: bad argument");
+    return sort_indices(ctx, keys, n_keys, ascending, nullptr, out_perm);
+}
+
+extern "C" int qeh_sort_indices_nulls(qeh_ctx *ctx, const qeh_column *keys, int n_keys, const int8_t *ascending,
+                                      const int8_t *nulls_first, qeh_column *out_perm) {
+    if (!ctx || !keys || !out_perm) return fail(QEH_E_INVALID, "qeh_sort_indices_nulls: bad argument");
+    return sort_indices(ctx, keys, n_keys, ascending, nulls_first, out_perm);
 }
 
 // ---- payload-carrying sort (qeh_merge_sorted of one Int64 / Int32 key and one 8-byte column) ----
@@ -2316,25 +1539,6 @@ int qeh::sort_pairs_payload_parts(qeh_ctx *ctx, const qeh_column *keys, const qe
     return QEH_OK;
 }
 
-extern "C" int qeh_sort_indices_nulls(qeh_ctx *ctx, const qeh_column *keys, int n_keys, const int8_t *ascending,
-                                      const int8_t *nulls_first, qeh_column *out_perm) {
-    if (!ctx || !keys || !out_perm) return fail(QEH_E_INVALID, "qeh_sort_indices_nulls: bad argument");
-    DeviceGuard dg(ctx->device);
-    if (any_utf8(keys, n_keys)) {
-        Utf8Keys uk;
-        QEH_TRY(encode_utf8_keys(ctx, keys, n_keys, &uk));
-        return qeh_sort_indices_nulls(ctx, uk.keys.data(), n_keys, ascending, nulls_first, out_perm);
-    }
-    int64_t n;
-    QEH_TRY(check_sort_keys(keys, n_keys, &n));
-    RadixState rs;
-    QEH_TRY(sort_perm(ctx, keys, n_keys, ascending, n, rs, nulls_first));
-    QEH_TRY(alloc_column(ctx, QEH_DT_UINT32, n, false, out_perm));
-    if (n > 0) QEH_HIP(hipMemcpyAsync(out_perm->values, rs.v[rs.cur].p, (size_t)n * 4, hipMemcpyDeviceToDevice, ctx->stream));
-    QEH_HIP(hipStreamSynchronize(ctx->stream));
-    return QEH_OK;
-}
-
 extern "C" int qeh_take(qeh_ctx *ctx, const qeh_column *col, const qeh_column *indices, qeh_column *out) {
     if (!ctx || !col || !indices || !out) return fail(QEH_E_INVALID, "qeh_take: bad argument");
     DeviceGuard dg(ctx->device);
@@ -2361,856 +1565,6 @@ extern "C" int qeh_take(qeh_ctx *ctx, const qeh_column *col, const qeh_column *i
     QEH_TRY(gather_column(ctx, *col, idx.as<uint32_t>(), m, out));
     QEH_HIP(hipStreamSynchronize(ctx->stream));
     return QEH_OK;
-}
-
-extern "C" int qeh_row_number(qeh_ctx *ctx, const qeh_column *part_keys, int n_part, const qeh_column *order_keys,
-                              int n_order, const int8_t *ascending, qeh_column *out_rn) {
-    if (!ctx || !out_rn || (n_part + n_order) < 1) return fail(QEH_E_INVALID, "qeh_row_number: bad argument");
-    if (n_part > kMaxGroupKeys) return fail(QEH_E_UNSUPPORTED, "at most 4 PARTITION BY keys on the device");
-    DeviceGuard dg(ctx->device);
-    if (any_utf8(part_keys, n_part) || any_utf8(order_keys, n_order)) {
-        Utf8Keys pk, ok;
-        QEH_TRY(encode_utf8_keys(ctx, part_keys, n_part, &pk));
-        QEH_TRY(encode_utf8_keys(ctx, order_keys, n_order, &ok));
-        return qeh_row_number(ctx, pk.keys.data(), n_part, ok.keys.data(), n_order, ascending, out_rn);
-    }
-    std::vector<qeh_column> all;
-    std::vector<int8_t> asc;
-    for (int j = 0; j < n_part; ++j) {
-        all.push_back(part_keys[j]);
-        asc.push_back(1);
-    }
-    for (int j = 0; j < n_order; ++j) {
-        all.push_back(order_keys[j]);
-        asc.push_back(ascending ? ascending[j] : 1);
-    }
-    int64_t n;
-    QEH_TRY(check_sort_keys(all.data(), (int)all.size(), &n));
-    if (n_part >= 1 && n_order == 1) {  // bounded integer partition keys: partition instead of sorting
-        const int s = window_msd_keys(ctx, QEH_WIN_ROW_NUMBER, part_keys, n_part, order_keys[0], asc[n_part] != 0, 0, nullptr,
-                                      nullptr, out_rn);
-        if (s != kWindowMsdNotEligible) return s;
-    }
-    RadixState rs;
-    QEH_TRY(sort_perm(ctx, all.data(), (int)all.size(), asc.data(), n, rs));
-    QEH_TRY(alloc_column(ctx, QEH_DT_INT64, n, false, out_rn));
-    if (n == 0) return QEH_OK;
-    const uint32_t *perm = rs.v[rs.cur].as<uint32_t>();
-    DevBuf flags, seg;
-    int s = flags.alloc(ctx, (size_t)n * 4);
-    if (s != QEH_OK) {
-        qeh_column_release(ctx, out_rn);
-        return s;
-    }
-    KeyCols pk{};
-    pk.n = n_part;
-    for (int j = 0; j < n_part; ++j) pk.c[j] = make_colref(part_keys[j]);
-    const int grid = grid_for(ctx, n, kBlock * 8, 8);
-    {
-        KernelTimer kt(ctx, "row_number");
-        const int sh = rs.part_shift >= 0 ? rs.part_shift : 0;
-        const bool enc_ok = n_part == 1 && (rs.enc_injective || (rs.part_shift >= 0 && n_order == 1));
-        if (enc_ok && rs.key32)
-            hipLaunchKernelGGL(k_part_flags_enc<uint32_t>, dim3(grid), dim3(kBlock), 0, ctx->stream,
-                               rs.k[rs.cur].as<uint32_t>(), n, flags.as<uint32_t>(), sh);
-        else if (enc_ok)
-            hipLaunchKernelGGL(k_part_flags_enc<uint64_t>, dim3(grid), dim3(kBlock), 0, ctx->stream,
-                               rs.k[rs.cur].as<uint64_t>(), n, flags.as<uint32_t>(), sh);
-        else
-            hipLaunchKernelGGL(k_part_flags, dim3(grid), dim3(kBlock), 0, ctx->stream, pk, perm, n, flags.as<uint32_t>());
-    }
-    const int64_t nchunks = (n + kRnChunk - 1) / kRnChunk;
-    s = seg.alloc(ctx, (size_t)nchunks * 8);
-    if (s != QEH_OK) {
-        qeh_column_release(ctx, out_rn);
-        return s;
-    }
-    {
-        KernelTimer kt(ctx, "row_number");
-        hipLaunchKernelGGL(k_rn_chunk_last, dim3(gc_of(ctx, nchunks)), dim3(kBlock), 0, ctx->stream, flags.as<uint32_t>(), n, nchunks,
-                           seg.as<int64_t>());
-        hipLaunchKernelGGL(k_rn_prefix_max, dim3(1), dim3(1024), 0, ctx->stream, seg.as<int64_t>(), nchunks);
-    }
-    const int dbits = bit_length((uint64_t)(n - 1));
-    // Direct scatter by default.  QEH_RN_WINDOWED (experiment, slower): group the (destination,
-    // rn) pairs into 2 MB output windows with two radix passes and scatter window by window with
-    // the workgroups of one XCD per window — 138 vs 104 ms for cfg 5 (the passes cost 23 ms and
-    // the windowed scatter did not beat the direct one; with one pass and 32 MB windows: 61 vs
-    // 40 ms for the row-number stage).
-    if (dbits <= 22 || !std::getenv("QEH_RN_WINDOWED")) {
-        KernelTimer kt(ctx, "row_number");
-        hipLaunchKernelGGL(k_rn_write<false>, dim3(gc_of(ctx, nchunks)), dim3(kBlock), 0, ctx->stream, flags.as<uint32_t>(),
-                           seg.as<int64_t>(), perm, n, nchunks, (int64_t *)out_rn->values, nullptr, nullptr);
-    } else {
-        // (destination, rn) pairs in sorted order into the spare radix buffers, one stable 8-bit
-        // pass on the destination's top bits (windows of 2^(dbits-8) rows), windowed scatter
-        const int o = 1 - rs.cur;
-        {
-            KernelTimer kt(ctx, "row_number");
-            hipLaunchKernelGGL(k_rn_write<true>, dim3(gc_of(ctx, nchunks)), dim3(kBlock), 0, ctx->stream,
-                               flags.as<uint32_t>(), seg.as<int64_t>(), perm, n, nchunks, nullptr, rs.k[o].as<uint32_t>(),
-                               rs.v[o].as<uint32_t>());
-        }
-        rs.cur = o;
-        rs.key32 = true;
-        // 2 MB output windows (2^18 rows): two stable passes on destination bits [dbits-12, dbits)
-        const int wshift = dbits - 12;
-        s = radix_pass_at<uint32_t>(ctx, rs, wshift);
-        if (s == QEH_OK) s = radix_pass_at<uint32_t>(ctx, rs, wshift + 8);
-        DevBuf starts;
-        const int64_t nwin = (int64_t)(((uint64_t)(n - 1) >> wshift) + 1);
-        if (s == QEH_OK) s = starts.alloc(ctx, (size_t)(nwin + 1) * 8);
-        if (s != QEH_OK) {
-            qeh_column_release(ctx, out_rn);
-            return s;
-        }
-        KernelTimer kt(ctx, "row_number");
-        hipLaunchKernelGGL(k_rn_window_starts, dim3(grid_for(ctx, n + 1, kBlock * 8, 8)), dim3(kBlock), 0, ctx->stream,
-                           rs.k[rs.cur].as<uint32_t>(), n, wshift, nwin, starts.as<int64_t>());
-        const int gx = (int)std::max<int64_t>(8, ctx->props.multiProcessorCount * 4 / 8 * 8);
-        hipLaunchKernelGGL(k_rn_scatter_xcd, dim3(gx), dim3(kBlock), 0, ctx->stream, rs.k[rs.cur].as<uint32_t>(),
-                           rs.v[rs.cur].as<uint32_t>(), starts.as<int64_t>(), nwin, (int64_t *)out_rn->values);
-    }
-    QEH_HIP(hipGetLastError());
-    QEH_HIP(hipStreamSynchronize(ctx->stream));
-    return QEH_OK;
-}
-
-// ---- RANK / DENSE_RANK / NTILE / LAG / LEAD / FIRST_VALUE / LAST_VALUE -------------------
-// Same sorted order as ROW_NUMBER.  In sorted positions: ps[i] = start of i's partition and
-// qs[i] = start of its peer group (last flagged position <= i: the chunked max-scan of the row
-// numbers), peer-group counts by an exclusive scan (DENSE_RANK), partition ends stored at their
-// start (NTILE / LEAD / LAST_VALUE); one kernel then writes every row's result into input order.
-
-// L[i] = last j <= i with flags[j] (k_rn_write's scan, writing the start instead of i - start + 1)
-__global__ __launch_bounds__(kBlock) void k_seg_start(const uint32_t *__restrict__ flags, const int64_t *__restrict__ carry,
-                                                      int64_t n, int64_t nchunks, int64_t *__restrict__ L) {
-    __shared__ int64_t wmax[kBlock / 64];
-    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
-    for (int64_t c = blockIdx.x; c < nchunks; c += gridDim.x) {
-        const int64_t base = c * kRnChunk + (int64_t)t * kRnPer;
-        uint32_t f[kRnPer];
-        int64_t m = -1;
-#pragma unroll
-        for (int j = 0; j < kRnPer; ++j) {
-            const int64_t i = base + j;
-            f[j] = i < n ? flags[i] : 0u;
-            if (f[j]) m = i;
-        }
-        int64_t incl = m;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const int64_t o = __shfl_up(incl, d, 64);
-            if (lane >= d) incl = o > incl ? o : incl;
-        }
-        if (lane == 63) wmax[w] = incl;
-        __syncthreads();
-        int64_t start = carry[c];
-        for (int q = 0; q < w; ++q) start = wmax[q] > start ? wmax[q] : start;
-        const int64_t prev = __shfl_up(incl, 1, 64);
-        if (lane > 0) start = prev > start ? prev : start;
-#pragma unroll
-        for (int j = 0; j < kRnPer; ++j) {
-            const int64_t i = base + j;
-            if (f[j]) start = i;
-            if (i < n) L[i] = start;
-        }
-        __syncthreads();
-    }
-}
-
-__global__ void k_or_flags(uint32_t *__restrict__ a, const uint32_t *__restrict__ b, int64_t n) {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-        a[i] |= b[i];
-}
-
-// pend[ps[i]] = end of i's partition, written by its last row
-__global__ void k_part_end(const uint32_t *__restrict__ fp, const int64_t *__restrict__ ps, int64_t n,
-                           int64_t *__restrict__ pend) {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-        if (i == n - 1 || fp[i + 1]) pend[ps[i]] = i + 1;
-}
-
-__global__ void k_win_iota(uint32_t *__restrict__ p, int64_t n) {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-        p[i] = (uint32_t)i;
-}
-
-struct WinArgs {
-    const uint32_t *perm;
-    const int64_t *ps, *qs, *pend;
-    const uint64_t *excl;  // exclusive scan of the peer flags
-    const uint32_t *fq;    // peer flags
-    ColRef arg;
-    int64_t param;
-    int64_t dflt;
-    int has_dflt;
-    int esz;               // argument element bytes (value functions)
-};
-
-template <int FUNC>
-__global__ void k_window_out(WinArgs a, int64_t n, void *__restrict__ out, uint8_t *__restrict__ valid8) {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t s = a.ps[i], row = a.perm[i];
-        int64_t v = 0, src = -1;
-        uint8_t ok = 1;
-        if (FUNC == QEH_WIN_ROW_NUMBER) {
-            v = i - s + 1;
-        } else if (FUNC == QEH_WIN_RANK) {
-            v = a.qs[i] - s + 1;
-        } else if (FUNC == QEH_WIN_DENSE_RANK) {
-            v = (int64_t)(a.excl[i] + a.fq[i] - a.excl[s]);
-        } else if (FUNC == QEH_WIN_NTILE) {
-            const int64_t size = a.pend[s] - s, r0 = i - s, q = size / a.param, r = size % a.param;
-            v = r0 < r * (q + 1) ? r0 / (q + 1) + 1 : r + (r0 - r * (q + 1)) / q + 1;
-        } else if (FUNC == QEH_WIN_LAG) {
-            src = a.param <= i - s ? (int64_t)a.perm[i - a.param] : -2;
-        } else if (FUNC == QEH_WIN_LEAD) {
-            src = a.param < a.pend[s] - i ? (int64_t)a.perm[i + a.param] : -2;  // no i + param overflow
-        } else if (FUNC == QEH_WIN_FIRST_VALUE) {
-            src = a.perm[s];
-        } else {  // LAST_VALUE: the partition's last row (whole-partition frame)
-            src = a.perm[a.pend[s] - 1];
-        }
-        if (FUNC >= QEH_WIN_LAG) {
-            if (src == -2) {
-                ok = (uint8_t)a.has_dflt;
-                v = a.dflt;
-            } else {
-                ok = col_valid(a.arg, src) ? 1 : 0;
-                v = a.esz == 8 ? ((const int64_t *)a.arg.values)[src] : (int64_t)((const uint32_t *)a.arg.values)[src];
-            }
-            valid8[row] = ok;
-            if (a.esz == 8) ((int64_t *)out)[row] = ok ? v : 0;
-            else ((uint32_t *)out)[row] = ok ? (uint32_t)v : 0u;
-        } else {
-            ((int64_t *)out)[row] = v;
-        }
-    }
-}
-
-extern "C" int qeh_window(qeh_ctx *ctx, int32_t func, const qeh_column *part_keys, int n_part, const qeh_column *order_keys,
-                          int n_order, const int8_t *ascending, const qeh_column *arg, int64_t param, const int64_t *dflt,
-                          qeh_column *out) {
-    if (!ctx || !out || n_part < 0 || n_order < 0) return fail(QEH_E_INVALID, "qeh_window: bad argument");
-    if (func < QEH_WIN_ROW_NUMBER || func > QEH_WIN_LAST_VALUE) return fail(QEH_E_INVALID, "qeh_window: unknown function");
-    if (n_part > kMaxGroupKeys || n_order > kMaxGroupKeys)
-        return fail(QEH_E_UNSUPPORTED, "at most 4 PARTITION BY and 4 ORDER BY keys on the device");
-    const bool value_fn = func >= QEH_WIN_LAG;
-    if (func == QEH_WIN_NTILE && param < 1) return fail(QEH_E_INVALID, "NTILE needs a bucket count >= 1");
-    if ((func == QEH_WIN_LAG || func == QEH_WIN_LEAD) && param < 0) return fail(QEH_E_INVALID, "LAG/LEAD offset must be >= 0");
-    int esz = 8;
-    if (value_fn) {
-        if (!arg) return fail(QEH_E_INVALID, "window value function needs an argument column");
-        QEH_TRY(check_column(*arg, "window argument"));
-        if (arg->dtype == QEH_DT_INT32 || arg->dtype == QEH_DT_FLOAT32) esz = 4;
-        else if (arg->dtype != QEH_DT_INT64 && arg->dtype != QEH_DT_FLOAT64)
-            return fail(QEH_E_UNSUPPORTED, "window value functions take Int32/Int64/Float32/Float64 on the device");
-    }
-    DeviceGuard dg(ctx->device);
-    if (any_utf8(part_keys, n_part) || any_utf8(order_keys, n_order)) {  // Utf8 `arg` stays unsupported (above)
-        Utf8Keys pk, ok;
-        QEH_TRY(encode_utf8_keys(ctx, part_keys, n_part, &pk));
-        QEH_TRY(encode_utf8_keys(ctx, order_keys, n_order, &ok));
-        return qeh_window(ctx, func, pk.keys.data(), n_part, ok.keys.data(), n_order, ascending, arg, param, dflt, out);
-    }
-    std::vector<qeh_column> all;
-    std::vector<int8_t> asc;
-    for (int j = 0; j < n_part; ++j) all.push_back(part_keys[j]), asc.push_back(1);
-    for (int j = 0; j < n_order; ++j) all.push_back(order_keys[j]), asc.push_back(ascending ? ascending[j] : 1);
-    int64_t n = arg ? arg->length : 0;  // OVER (): the argument column gives the row count
-    if (!all.empty()) {
-        QEH_TRY(check_sort_keys(all.data(), (int)all.size(), &n));
-        if (value_fn && arg->length != n) return fail(QEH_E_INVALID, "window argument length mismatch");
-    } else if (!arg) {
-        return fail(QEH_E_INVALID, "qeh_window: OVER () needs a column for the row count");
-    }
-    if (func == QEH_WIN_ROW_NUMBER && !all.empty())  // the dedicated path (pair-key sort, no peer state)
-        return qeh_row_number(ctx, part_keys, n_part, order_keys, n_order, ascending, out);
-    if (n_part >= 1 && n_order == 1) {  // bounded integer partition keys: partition instead of sorting
-        const int s = window_msd_keys(ctx, func, part_keys, n_part, order_keys[0], asc[n_part] != 0, param, arg, dflt, out);
-        if (s != kWindowMsdNotEligible) return s;
-    }
-    const int odt = value_fn ? arg->dtype : QEH_DT_INT64;
-    QEH_TRY(alloc_column(ctx, odt, n, value_fn, out));
-    if (n == 0) return QEH_OK;
-    auto bail = [&](int s) {
-        qeh_column_release(ctx, out);
-        return s;
-    };
-    RadixState rs;
-    DevBuf iota;
-    const uint32_t *perm;
-    if (!all.empty()) {
-        int s = sort_perm(ctx, all.data(), (int)all.size(), asc.data(), n, rs);
-        if (s != QEH_OK) return bail(s);
-        perm = rs.v[rs.cur].as<uint32_t>();
-    } else {
-        if (iota.alloc(ctx, (size_t)n * 4) != QEH_OK) return bail(QEH_E_OOM);
-        hipLaunchKernelGGL(k_win_iota, dim3(grid_for(ctx, n, kBlock * 8, 8)), dim3(kBlock), 0, ctx->stream, iota.as<uint32_t>(), n);
-        perm = iota.as<uint32_t>();
-    }
-    const int grid = grid_for(ctx, n, kBlock * 8, 8);
-    const int64_t nchunks = (n + kRnChunk - 1) / kRnChunk;
-    DevBuf fp, fq, ps, qs, pend, excl, carry, valid8;
-    if (fp.alloc(ctx, (size_t)n * 4) != QEH_OK || ps.alloc(ctx, (size_t)n * 8) != QEH_OK ||
-        carry.alloc(ctx, (size_t)nchunks * 8) != QEH_OK)
-        return bail(QEH_E_OOM);
-    KernelTimer kt(ctx, "window");
-    KeyCols pk{};
-    pk.n = n_part;
-    for (int j = 0; j < n_part; ++j) pk.c[j] = make_colref(part_keys[j]);
-    // partition flags from the sorted encodings when they determine the partition key (as in
-    // qeh_row_number), else by comparing the key columns through the permutation
-    const int sh = rs.part_shift >= 0 ? rs.part_shift : 0;
-    const bool enc_ok = !all.empty() && n_part == 1 && (rs.enc_injective || (rs.part_shift >= 0 && n_order == 1));
-    if (enc_ok && rs.key32)
-        hipLaunchKernelGGL(k_part_flags_enc<uint32_t>, dim3(grid), dim3(kBlock), 0, ctx->stream, rs.k[rs.cur].as<uint32_t>(), n,
-                           fp.as<uint32_t>(), sh);
-    else if (enc_ok)
-        hipLaunchKernelGGL(k_part_flags_enc<uint64_t>, dim3(grid), dim3(kBlock), 0, ctx->stream, rs.k[rs.cur].as<uint64_t>(), n,
-                           fp.as<uint32_t>(), sh);
-    else
-        hipLaunchKernelGGL(k_part_flags, dim3(grid), dim3(kBlock), 0, ctx->stream, pk, perm, n, fp.as<uint32_t>());
-    auto seg_start = [&](const uint32_t *flags, int64_t *L) {
-        hipLaunchKernelGGL(k_rn_chunk_last, dim3(gc_of(ctx, nchunks)), dim3(kBlock), 0, ctx->stream, flags, n, nchunks,
-                           carry.as<int64_t>());
-        hipLaunchKernelGGL(k_rn_prefix_max, dim3(1), dim3(1024), 0, ctx->stream, carry.as<int64_t>(), nchunks);
-        hipLaunchKernelGGL(k_seg_start, dim3(gc_of(ctx, nchunks)), dim3(kBlock), 0, ctx->stream, flags, carry.as<int64_t>(), n,
-                           nchunks, L);
-    };
-    seg_start(fp.as<uint32_t>(), ps.as<int64_t>());
-    WinArgs a{};
-    a.perm = perm;
-    a.ps = ps.as<int64_t>();
-    a.param = param;
-    a.esz = esz;
-    if (func == QEH_WIN_RANK || func == QEH_WIN_DENSE_RANK) {
-        // peer flags: partition start or any ORDER BY key changes
-        if (fq.alloc(ctx, (size_t)n * 4) != QEH_OK) return bail(QEH_E_OOM);
-        KeyCols ok{};
-        ok.n = n_order;
-        for (int j = 0; j < n_order; ++j) ok.c[j] = make_colref(order_keys[j]);
-        if (n_order > 0) {
-            hipLaunchKernelGGL(k_part_flags, dim3(grid), dim3(kBlock), 0, ctx->stream, ok, perm, n, fq.as<uint32_t>());
-            hipLaunchKernelGGL(k_or_flags, dim3(grid), dim3(kBlock), 0, ctx->stream, fq.as<uint32_t>(), fp.as<uint32_t>(), n);
-        } else if (hipMemcpyAsync(fq.p, fp.p, (size_t)n * 4, hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess) {
-            return bail(fail(QEH_E_HIP, "qeh_window: device copy failed"));
-        }
-        a.fq = fq.as<uint32_t>();
-        if (func == QEH_WIN_RANK) {
-            if (qs.alloc(ctx, (size_t)n * 8) != QEH_OK) return bail(QEH_E_OOM);
-            seg_start(fq.as<uint32_t>(), qs.as<int64_t>());
-            a.qs = qs.as<int64_t>();
-        } else {
-            if (excl.alloc(ctx, (size_t)n * 8) != QEH_OK) return bail(QEH_E_OOM);
-            int s = exclusive_scan_u32(ctx, fq.as<uint32_t>(), excl.as<uint64_t>(), n, nullptr);
-            if (s != QEH_OK) return bail(s);
-            a.excl = excl.as<uint64_t>();
-        }
-    }
-    if (func == QEH_WIN_NTILE || func == QEH_WIN_LEAD || func == QEH_WIN_LAST_VALUE) {
-        if (pend.alloc(ctx, (size_t)n * 8) != QEH_OK) return bail(QEH_E_OOM);
-        hipLaunchKernelGGL(k_part_end, dim3(grid), dim3(kBlock), 0, ctx->stream, fp.as<uint32_t>(), ps.as<int64_t>(), n,
-                           pend.as<int64_t>());
-        a.pend = pend.as<int64_t>();
-    }
-    if (value_fn) {
-        if (valid8.alloc(ctx, (size_t)n) != QEH_OK) return bail(QEH_E_OOM);
-        a.arg = make_colref(*arg);
-        a.has_dflt = dflt != nullptr;
-        if (dflt) a.dflt = esz == 8 ? *dflt : (int64_t)(uint32_t)*dflt;
-    }
-#define QEH_WIN(F)                                                                                                        \
-    hipLaunchKernelGGL(k_window_out<F>, dim3(grid), dim3(kBlock), 0, ctx->stream, a, n, out->values, valid8.as<uint8_t>())
-    switch (func) {
-        case QEH_WIN_ROW_NUMBER: QEH_WIN(QEH_WIN_ROW_NUMBER); break;  // OVER (): input order
-        case QEH_WIN_RANK: QEH_WIN(QEH_WIN_RANK); break;
-        case QEH_WIN_DENSE_RANK: QEH_WIN(QEH_WIN_DENSE_RANK); break;
-        case QEH_WIN_NTILE: QEH_WIN(QEH_WIN_NTILE); break;
-        case QEH_WIN_LAG: QEH_WIN(QEH_WIN_LAG); break;
-        case QEH_WIN_LEAD: QEH_WIN(QEH_WIN_LEAD); break;
-        case QEH_WIN_FIRST_VALUE: QEH_WIN(QEH_WIN_FIRST_VALUE); break;
-        default: QEH_WIN(QEH_WIN_LAST_VALUE); break;
-    }
-#undef QEH_WIN
-    if (hipGetLastError() != hipSuccess) return bail(fail(QEH_E_HIP, "qeh_window: kernel launch failed"));
-    if (value_fn) {
-        int s = qeh_bytes_to_validity(ctx, valid8.as<uint8_t>(), n, out->validity);
-        if (s != QEH_OK) return bail(s);
-        out->null_count = -1;
-    }
-    if (hipStreamSynchronize(ctx->stream) != hipSuccess) return bail(fail(QEH_E_HIP, "qeh_window: stream synchronize failed"));
-    return QEH_OK;
-}
-
-// Stable partition-major permutation from per-row partition ids written by `ids`.
-template <typename IdLaunch>
-static int partition_perm(qeh_ctx *ctx, int64_t n, int n_parts, IdLaunch ids, const char *timer, int64_t *counts,
-                          qeh_column *out_perm) {
-    RadixState rs;
-    rs.n = n;
-    for (int b = 0; b < 2; ++b) {
-        QEH_TRY(rs.k[b].alloc(ctx, (size_t)std::max<int64_t>(n, 1) * 8));
-        QEH_TRY(rs.v[b].alloc(ctx, (size_t)std::max<int64_t>(n, 1) * 4));
-    }
-    std::fill(counts, counts + n_parts, 0);
-    if (n > 0) {
-        {
-            KernelTimer kt(ctx, timer);
-            ids(rs.k[0].as<uint64_t>(), rs.v[0].as<uint32_t>());
-        }
-        QEH_HIP(hipGetLastError());
-        QEH_TRY(radix_passes(ctx, rs, n_parts > 1 ? bit_length((uint64_t)n_parts - 1) : 0));
-    }
-    QEH_TRY(alloc_column(ctx, QEH_DT_UINT32, n, false, out_perm));
-    if (n > 0) {
-        QEH_HIP(hipMemcpyAsync(out_perm->values, rs.v[rs.cur].p, (size_t)n * 4, hipMemcpyDeviceToDevice, ctx->stream));
-        DevBuf cnt;
-        int s = cnt.alloc(ctx, (size_t)n_parts * 8);
-        if (s == QEH_OK) {
-            QEH_HIP(hipMemsetAsync(cnt.p, 0, (size_t)n_parts * 8, ctx->stream));
-            hipLaunchKernelGGL(k_count_parts, dim3(grid_for(ctx, n, kBlock * 16, 4)), dim3(kBlock), 0, ctx->stream,
-                               rs.k[rs.cur].as<uint64_t>(), n, n_parts, cnt.as<unsigned long long>());
-            s = read_small(ctx, counts, cnt.p, (size_t)n_parts * 8);
-        }
-        if (s != QEH_OK) {
-            qeh_column_release(ctx, out_perm);
-            return s;
-        }
-    }
-    QEH_HIP(hipStreamSynchronize(ctx->stream));
-    return QEH_OK;
-}
-
-extern "C" int qeh_hash_partition(qeh_ctx *ctx, const qeh_column *key, int n_parts, int64_t *counts,
-                                  qeh_column *out_perm) {
-    if (!ctx || !key || !counts || !out_perm || n_parts < 1 || n_parts > kRadix)
-        return fail(QEH_E_INVALID, "qeh_hash_partition: bad argument (1..256 partitions)");
-    DeviceGuard dg(ctx->device);
-    QEH_TRY(check_column(*key, "partition key"));
-    if (key->dtype != QEH_DT_INT64 && key->dtype != QEH_DT_INT32)
-        return fail(QEH_E_UNSUPPORTED, "partition keys must be Int32/Int64 on the device");
-    const int64_t n = key->length;
-    const ColRef kc = make_colref(*key);
-    return partition_perm(
-        ctx, n, n_parts,
-        [&](uint64_t *ids, uint32_t *idx) {
-            hipLaunchKernelGGL(k_partition_ids, dim3(grid_for(ctx, n, kBlock * 8, 8)), dim3(kBlock), 0, ctx->stream, kc,
-                               n, (uint32_t)n_parts, ids, idx);
-        },
-        "hash_partition", counts, out_perm);
-}
-
-extern "C" int qeh_range_partition(qeh_ctx *ctx, const qeh_column *key, int ascending, const int64_t *splitters,
-                                   int n_splitters, int64_t *counts, qeh_column *out_perm) {
-    if (!ctx || !key || !counts || !out_perm || n_splitters < 0 || n_splitters >= kRadix ||
-        (n_splitters > 0 && !splitters))
-        return fail(QEH_E_INVALID, "qeh_range_partition: bad argument (0..255 splitters)");
-    DeviceGuard dg(ctx->device);
-    QEH_TRY(check_column(*key, "partition key"));
-    if (key->dtype == QEH_DT_UTF8) return fail(QEH_E_UNSUPPORTED, "Utf8 range partition keys are not supported on the device");
-    for (int j = 1; j < n_splitters; ++j)
-        if (splitters[j] < splitters[j - 1]) return fail(QEH_E_INVALID, "qeh_range_partition: splitters must be ascending");
-    const int64_t n = key->length;
-    DevBuf sp;
-    QEH_TRY(sp.alloc(ctx, (size_t)std::max(n_splitters, 1) * 8));
-    if (n_splitters > 0)
-        QEH_HIP(hipMemcpyAsync(sp.p, splitters, (size_t)n_splitters * 8, hipMemcpyHostToDevice, ctx->stream));
-    QEH_HIP(hipStreamSynchronize(ctx->stream));  // host splitter array may go away
-    const ColRef kc = make_colref(*key);
-    return partition_perm(
-        ctx, n, n_splitters + 1,
-        [&](uint64_t *ids, uint32_t *idx) {
-            hipLaunchKernelGGL(k_range_ids, dim3(grid_for(ctx, n, kBlock * 8, 8)), dim3(kBlock), 0, ctx->stream, kc, n,
-                               sp.as<int64_t>(), n_splitters, ascending ? 1 : 0, ids, idx);
-        },
-        "range_partition", counts, out_perm);
-}
-
-extern "C" int qeh_partition_hash(qeh_ctx *ctx, const qeh_column *keys, int n_keys, int n_parts, int64_t *counts,
-                                  qeh_column *out_perm) {
-    if (!ctx || !keys || n_keys < 1 || n_keys > kMaxCols || !counts || !out_perm || n_parts < 1 || n_parts > kRadix)
-        return fail(QEH_E_INVALID, "qeh_partition_hash: bad argument (1..12 keys, 1..256 partitions)");
-    DeviceGuard dg(ctx->device);
-    HashKeys hk{};
-    hk.n = n_keys;
-    const int64_t n = keys[0].length;
-    for (int j = 0; j < n_keys; ++j) {
-        QEH_TRY(check_column(keys[j], "partition key"));
-        if (keys[j].length != n) return fail(QEH_E_INVALID, "partition keys have different lengths");
-        if (keys[j].dtype != QEH_DT_INT64 && keys[j].dtype != QEH_DT_INT32 && keys[j].dtype != QEH_DT_UTF8)
-            return fail(QEH_E_UNSUPPORTED, "hash partition keys must be Int32 / Int64 / Utf8 (compute_row_hash)");
-        hk.c[j] = make_colref(keys[j]);
-        if (keys[j].dtype == QEH_DT_UTF8) {
-            hk.offs[j] = keys[j].offsets + keys[j].offset;
-            hk.data[j] = (const uint8_t *)keys[j].values;
-        }
-    }
-    return partition_perm(
-        ctx, n, n_parts,
-        [&](uint64_t *ids, uint32_t *idx) {
-            hipLaunchKernelGGL(k_hash_ids_multi, dim3(grid_for(ctx, n, kBlock * 8, 8)), dim3(kBlock), 0, ctx->stream, hk, n,
-                               (uint32_t)n_parts, ids, idx);
-        },
-        "hash_partition", counts, out_perm);
-}
-
-static int make_hash_keys(const qeh_column *keys, int n_keys, HashKeys *hk, int64_t *n) {
-    hk->n = n_keys;
-    *n = keys[0].length;
-    for (int j = 0; j < n_keys; ++j) {
-        QEH_TRY(check_column(keys[j], "partition key"));
-        if (keys[j].length != *n) return fail(QEH_E_INVALID, "partition keys have different lengths");
-        if (keys[j].dtype != QEH_DT_INT64 && keys[j].dtype != QEH_DT_INT32 && keys[j].dtype != QEH_DT_UTF8)
-            return fail(QEH_E_UNSUPPORTED, "hash partition keys must be Int32 / Int64 / Utf8 (compute_row_hash)");
-        hk->c[j] = make_colref(keys[j]);
-        if (keys[j].dtype == QEH_DT_UTF8) {
-            hk->offs[j] = keys[j].offsets + keys[j].offset;
-            hk->data[j] = (const uint8_t *)keys[j].values;
-        }
-    }
-    return QEH_OK;
-}
-
-// Exchange's device side in one pass: partition ids, per-segment histograms, then the payload
-// columns moved to partition-major order (k_part_scatter).  Columns that are not non-null
-// 8-byte go through the permutation + gather path.
-// qeh_partition_hash_unmove: out_cols[c][i] = moved[c][position of row i in the stable partition-major
-// order of qeh_partition_hash_move over the same key] -- the reverse of an Exchange's move, for results
-// computed on the partition-major rows (distributed window functions return them into input order).
-extern "C" int qeh_partition_hash_unmove(qeh_ctx *ctx, const qeh_column *key, int n_parts, const qeh_column *moved,
-                                         int n_cols, qeh_column *out_cols) {
-    if (!ctx || !key || !moved || !out_cols || n_cols < 1 || n_cols > 2 || n_parts < 1 || n_parts > kPsDig)
-        return fail(QEH_E_INVALID, "qeh_partition_hash_unmove: bad argument (1..2 columns, 1..16 partitions)");
-    DeviceGuard dg(ctx->device);
-    const int64_t n = key->length;
-    QEH_TRY(check_column(*key, "partition key"));
-    if (key->dtype != QEH_DT_INT64 || (key->validity && key->null_count != 0) ||
-        (((uintptr_t)key->values + (uintptr_t)key->offset * 8) & 15) != 0)
-        return fail(QEH_E_UNSUPPORTED, "qeh_partition_hash_unmove: one non-null, 16-B aligned Int64 key");
-    for (int c = 0; c < n_cols; ++c) {
-        QEH_TRY(check_column(moved[c], "moved column"));
-        if (moved[c].length != n || (moved[c].dtype != QEH_DT_INT64 && moved[c].dtype != QEH_DT_FLOAT64) ||
-            (moved[c].validity && moved[c].null_count != 0))
-            return fail(QEH_E_UNSUPPORTED, "qeh_partition_hash_unmove: non-null Int64 / Float64 columns of the key's length");
-    }
-    constexpr int64_t kFusedTile = (int64_t)kRsThreads * kFastR;
-    int nblocks = (int)std::min<int64_t>(std::max<int64_t>((n + kFusedTile - 1) / kFusedTile, 1), (int64_t)ctx->props.multiProcessorCount);
-    int64_t seg = (n + nblocks - 1) / nblocks;
-    seg = std::max<int64_t>((seg + kFusedTile - 1) / kFusedTile * kFusedTile, kFusedTile);
-    nblocks = (int)std::max<int64_t>((n + seg - 1) / seg, 1);
-    int made = 0, s = QEH_OK;
-    for (; made < n_cols; ++made)
-        if ((s = alloc_column(ctx, moved[made].dtype, n, false, &out_cols[made])) != QEH_OK) break;
-    if (s == QEH_OK && n > 0) {
-        DevBuf ids, hist, offs;
-        if (ids.alloc(ctx, (size_t)n) || hist.alloc(ctx, (size_t)kPsDig * nblocks * 4) ||
-            offs.alloc(ctx, (size_t)kPsDig * nblocks * 8))
-            s = fail(QEH_E_OOM, "partition unmove: out of device memory");
-        KernelTimer kt(ctx, "partition_move");
-        if (s == QEH_OK) {
-            FastIn fin{};
-            fin.key = (const int64_t *)key->values + key->offset;
-            hipLaunchKernelGGL(k_ids_hist_pred<0>, dim3(nblocks), dim3(kRsThreads), 0, ctx->stream, fin, PredTerms{}, n, seg,
-                               (uint32_t)n_parts, ids.as<uint8_t>(), hist.as<uint32_t>(), nblocks);
-            s = exclusive_scan_u32(ctx, hist.as<uint32_t>(), offs.as<uint64_t>(), (int64_t)kPsDig * nblocks, nullptr);
-        }
-        if (s == QEH_OK) {
-            PmCols pc{};
-            pc.n = n_cols;
-            for (int c = 0; c < n_cols; ++c) {
-                pc.src[c] = (const uint64_t *)moved[c].values + moved[c].offset;
-                pc.dst[c] = (uint64_t *)out_cols[c].values;
-            }
-            const bool ballot = rs_ballot(ctx);
-            auto kf = n_cols == 1 ? (ballot ? k_part_gather_small<1, false> : k_part_gather_small<1, true>)
-                                  : (ballot ? k_part_gather_small<2, false> : k_part_gather_small<2, true>);
-            hipLaunchKernelGGL(kf, dim3(nblocks), dim3(kRsThreads), 0, ctx->stream, ids.as<uint8_t>(), n, seg,
-                               offs.as<uint64_t>(), nblocks, pc);
-            if (hipGetLastError() != hipSuccess) s = fail(QEH_E_HIP, "partition unmove launch failed");
-        }
-        if (s == QEH_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) s = fail(QEH_E_HIP, "partition unmove failed");
-    }
-    if (s != QEH_OK)
-        for (int c = 0; c < made; ++c) qeh_column_release(ctx, &out_cols[c]);
-    return s;
-}
-
-extern "C" int qeh_partition_hash_move(qeh_ctx *ctx, const qeh_column *keys, int n_keys, int n_parts,
-                                       const qeh_column *cols, int n_cols, int64_t *counts, qeh_column *out_cols) {
-    if (!ctx || !keys || n_keys < 1 || n_keys > kMaxCols || !counts || n_parts < 1 || n_parts > kRadix || n_cols < 0 ||
-        (n_cols > 0 && (!cols || !out_cols)))
-        return fail(QEH_E_INVALID, "qeh_partition_hash_move: bad argument (1..12 keys, 1..256 partitions)");
-    DeviceGuard dg(ctx->device);
-    HashKeys hk{};
-    int64_t n;
-    QEH_TRY(make_hash_keys(keys, n_keys, &hk, &n));
-    for (int c = 0; c < n_cols; ++c) {
-        QEH_TRY(check_column(cols[c], "partition column"));
-        if (cols[c].length != n) return fail(QEH_E_INVALID, "partition columns and keys have different lengths");
-    }
-    auto movable = [](const qeh_column &c) {
-        return (c.dtype == QEH_DT_INT64 || c.dtype == QEH_DT_FLOAT64) && (!c.validity || c.null_count == 0);
-    };
-    std::vector<int> mv, other;
-    for (int c = 0; c < n_cols; ++c) (movable(cols[c]) ? mv : other).push_back(c);
-    std::fill(counts, counts + n_parts, 0);
-    std::vector<char> made(n_cols, 0);
-    auto cleanup = [&]() {
-        for (int c = 0; c < n_cols; ++c)
-            if (made[c]) qeh_column_release(ctx, &out_cols[c]);
-    };
-    // one non-null, 16-B aligned Int64 key into at most kPsDig partitions: ids and per-segment
-    // histograms in one pass (k_ids_hist_pred without terms), segments of whole 8192-row tiles
-    const qeh_column &k0 = keys[0];
-    const bool fused = n_keys == 1 && n_parts <= kPsDig && k0.dtype == QEH_DT_INT64 &&
-                       (!k0.validity || k0.null_count == 0) &&
-                       (((uintptr_t)k0.values + (uintptr_t)k0.offset * 8) & 15) == 0 && !std::getenv("QEH_PM_GENERIC");
-    constexpr int64_t kFusedTile = (int64_t)kRsThreads * kFastR;
-    int nblocks = (int)std::min<int64_t>(std::max<int64_t>((n + kPmTile - 1) / kPmTile, 1),
-                                         (int64_t)ctx->props.multiProcessorCount);
-    int64_t seg = (n + nblocks - 1) / nblocks;
-    if (fused) {
-        seg = std::max<int64_t>((seg + kFusedTile - 1) / kFusedTile * kFusedTile, kFusedTile);
-        nblocks = (int)std::max<int64_t>((n + seg - 1) / seg, 1);
-    }
-    DevBuf ids, hist, offs;
-    QEH_TRY(ids.alloc(ctx, (size_t)std::max<int64_t>(n, 1)));
-    QEH_TRY(hist.alloc(ctx, (size_t)kRadix * nblocks * 4));
-    QEH_TRY(offs.alloc(ctx, (size_t)kRadix * nblocks * 8));
-    const int ndig = fused ? kPsDig : kRadix;  // digits the histogram holds (digit-major)
-    std::vector<uint32_t> h((size_t)ndig * nblocks, 0);
-    if (n > 0) {
-        KernelTimer kt(ctx, "partition_move");
-        if (fused) {
-            FastIn fin{};
-            fin.key = (const int64_t *)k0.values + k0.offset;
-            hipLaunchKernelGGL(k_ids_hist_pred<0>, dim3(nblocks), dim3(kRsThreads), 0, ctx->stream, fin, PredTerms{}, n,
-                               seg, (uint32_t)n_parts, ids.as<uint8_t>(), hist.as<uint32_t>(), nblocks);
-        } else {
-            if (n_keys == 1 && k0.dtype == QEH_DT_INT64 && (!k0.validity || k0.null_count == 0))
-                hipLaunchKernelGGL(k_hash_ids8_i64, dim3(grid_for(ctx, (n + 7) / 8, kBlock, 8)), dim3(kBlock), 0,
-                                   ctx->stream, (const int64_t *)k0.values + k0.offset, n, (uint32_t)n_parts,
-                                   ids.as<uint8_t>());
-            else
-                hipLaunchKernelGGL(k_hash_ids8, dim3(grid_for(ctx, n, kBlock * 8, 8)), dim3(kBlock), 0, ctx->stream, hk, n,
-                                   (uint32_t)n_parts, ids.as<uint8_t>());
-            hipLaunchKernelGGL(k_rs_hist_u8, dim3(nblocks), dim3(kRsThreads), 0, ctx->stream, ids.as<uint8_t>(), n, seg,
-                               hist.as<uint32_t>(), nblocks);  // ids are a byte stream: 16 per load
-        }
-        QEH_HIP(hipGetLastError());
-        QEH_TRY(exclusive_scan_u32(ctx, hist.as<uint32_t>(), offs.as<uint64_t>(), (int64_t)ndig * nblocks, nullptr));
-        QEH_TRY(read_small(ctx, h.data(), hist.p, h.size() * 4));
-        for (int p = 0; p < n_parts; ++p)
-            for (int b = 0; b < nblocks; ++b) counts[p] += h[(size_t)p * nblocks + b];
-    }
-    int s = QEH_OK;
-    for (int c : mv) {
-        if ((s = alloc_column(ctx, cols[c].dtype, n, false, &out_cols[c])) != QEH_OK) break;
-        made[c] = 1;
-    }
-    const bool small = n_parts <= kPsDig && !std::getenv("QEH_PM_GENERIC");
-    for (size_t g = 0; s == QEH_OK && g < mv.size() && n > 0; g += kPmMaxCols) {
-        PmCols pc{};
-        const int nc = (int)std::min<size_t>(kPmMaxCols, mv.size() - g);
-        pc.n = nc;
-        for (int q = 0; q < nc; ++q) {
-            const qeh_column &src = cols[mv[g + q]];
-            pc.src[q] = (const uint64_t *)src.values + src.offset;
-            pc.dst[q] = (uint64_t *)out_cols[mv[g + q]].values;
-        }
-        KernelTimer kt(ctx, "partition_move");
-#define QEH_PM(NCV, AT)                                                                                                       \
-    do {                                                                                                               \
-        if (small)                                                                                                     \
-            hipLaunchKernelGGL((k_part_scatter_small<NCV, AT>), dim3(nblocks), dim3(kRsThreads), 0, ctx->stream,             \
-                               ids.as<uint8_t>(), n, seg, offs.as<uint64_t>(), nblocks, pc, (uint32_t)kRadix);         \
-        else                                                                                                           \
-            hipLaunchKernelGGL((k_part_scatter<NCV, AT>), dim3(nblocks), dim3(kRsThreads), 0, ctx->stream, ids.as<uint8_t>(), \
-                               n, seg, offs.as<uint64_t>(), nblocks, pc, (uint32_t)kRadix);                            \
-    } while (0)
-        const bool ballot = rs_ballot(ctx);
-        if (nc == 1) { if (ballot) QEH_PM(1, false); else QEH_PM(1, true); }
-        else if (nc == 2) { if (ballot) QEH_PM(2, false); else QEH_PM(2, true); }
-        else if (nc == 3) { if (ballot) QEH_PM(3, false); else QEH_PM(3, true); }
-        else { if (ballot) QEH_PM(4, false); else QEH_PM(4, true); }
-#undef QEH_PM
-        if (hipGetLastError() != hipSuccess) s = fail(QEH_E_HIP, "partition move launch failed");
-    }
-    if (s == QEH_OK && !other.empty()) {  // permutation + gathers for the rest
-        int64_t c2[kRadix];
-        qeh_column perm{};
-        s = qeh_partition_hash(ctx, keys, n_keys, n_parts, c2, &perm);
-        for (size_t q = 0; s == QEH_OK && q < other.size(); ++q) {
-            s = gather_column(ctx, cols[other[q]], (const uint32_t *)perm.values, n, &out_cols[other[q]]);
-            if (s == QEH_OK) made[other[q]] = 1;
-        }
-        if (perm.owned) {
-            (void)hipStreamSynchronize(ctx->stream);
-            qeh_column_release(ctx, &perm);
-        }
-    }
-    if (s == QEH_OK) {
-        hipError_t e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) s = fail(QEH_E_HIP, std::string("partition move: ") + hipGetErrorString(e));
-    }
-    if (s != QEH_OK) cleanup();
-    return s;
-}
-
-// Filter + Exchange device side in two passes over the probe columns: partition ids of the
-// qualifying rows (k_hash_ids8_pred), per-segment histograms, then the moved columns written
-// partition-major with the rejected rows left out (k_part_scatter with a drop id).
-extern "C" int qeh_filter_partition_hash_move(qeh_ctx *ctx, const qeh_column *cols, int n_cols, const qeh_expr *predicate,
-                                              int key_idx, int n_parts, const int32_t *move_idx, int n_move,
-                                              int64_t *counts, qeh_column *out_cols) {
-    if (!ctx || !cols || n_cols < 1 || n_cols > kMaxCols || !predicate || key_idx < 0 || key_idx >= n_cols || !counts ||
-        n_parts < 1 || n_parts >= kRadix || n_move < 1 || n_move > kPmMaxCols || !move_idx || !out_cols)
-        return fail(QEH_E_INVALID, "qeh_filter_partition_hash_move: bad argument (1..255 partitions, 1..4 moved columns)");
-    DeviceGuard dg(ctx->device);
-    const int64_t n = cols[0].length;
-    for (int c = 0; c < n_cols; ++c) {
-        QEH_TRY(check_column(cols[c], "filter-partition column"));
-        if (cols[c].length != n) return fail(QEH_E_INVALID, "filter-partition columns have different lengths");
-    }
-    const qeh_column &kc = cols[key_idx];
-    if (kc.dtype != QEH_DT_INT64 && kc.dtype != QEH_DT_INT32)
-        return fail(QEH_E_UNSUPPORTED, "qeh_filter_partition_hash_move: the key must be Int32 / Int64");
-    for (int q = 0; q < n_move; ++q) {
-        if (move_idx[q] < 0 || move_idx[q] >= n_cols) return fail(QEH_E_INVALID, "moved column index out of range");
-        const qeh_column &c = cols[move_idx[q]];
-        if ((c.dtype != QEH_DT_INT64 && c.dtype != QEH_DT_FLOAT64) || (c.validity && c.null_count != 0))
-            return fail(QEH_E_UNSUPPORTED, "qeh_filter_partition_hash_move: moved columns must be non-null Int64 / Float64");
-    }
-    std::vector<int32_t> dts(n_cols);
-    for (int i = 0; i < n_cols; ++i) dts[i] = cols[i].dtype;
-    DevProgram prog;
-    QEH_TRY(compile_expr(predicate, dts.data(), n_cols, &prog));
-    if (prog.result_type != QEH_DT_BOOL) return fail(QEH_E_TYPE, "Filter predicate must return boolean");
-    PredTerms terms{};
-    if (!lower_to_terms(predicate, dts.data(), n_cols, &terms))
-        return fail(QEH_E_UNSUPPORTED, "qeh_filter_partition_hash_move: predicate is not a list of column-literal comparisons");
-    ColSet cs;
-    QEH_TRY(make_colset(cols, n_cols, &cs));
-    std::fill(counts, counts + n_parts, 0);
-    // the fused id + histogram pass: fewer than kPsDig partitions, a non-null Int64 key and term
-    // columns that are non-null 8-byte, 16-B aligned (FastTile's loads)
-    auto fast_ok = [](const qeh_column &c) {
-        return (c.dtype == QEH_DT_INT64 || c.dtype == QEH_DT_FLOAT64) && (!c.validity || c.null_count == 0) &&
-               (((uintptr_t)c.values + (uintptr_t)c.offset * 8) & 15) == 0;
-    };
-    bool fused = n_parts < kPsDig && kc.dtype == QEH_DT_INT64 && fast_ok(kc) && terms.n <= 2 &&
-                 !std::getenv("QEH_PM_GENERIC");
-    FastIn fin{};
-    if (fused) {
-        fin.key = (const int64_t *)kc.values + kc.offset;
-        for (int i = 0; i < terms.n; ++i) {
-            const qeh_column &tc = cols[terms.t[i].col];
-            if (!fast_ok(tc)) fused = false;
-            fin.term[i] = (const int64_t *)tc.values + tc.offset;
-            fin.term_dt[i] = tc.dtype;
-        }
-    }
-    constexpr int64_t kFusedTile = (int64_t)kRsThreads * kFastR;
-    int nblocks = (int)std::min<int64_t>(std::max<int64_t>((n + kPmTile - 1) / kPmTile, 1),
-                                         (int64_t)ctx->props.multiProcessorCount);
-    int64_t seg = (n + nblocks - 1) / nblocks;
-    if (fused) {  // segments of whole 8192-row tiles (16-B aligned pairs in every segment)
-        seg = std::max<int64_t>((seg + kFusedTile - 1) / kFusedTile * kFusedTile, kFusedTile);
-        nblocks = (int)std::max<int64_t>((n + seg - 1) / seg, 1);
-    }
-    DevBuf ids, hist, offs;
-    QEH_TRY(ids.alloc(ctx, (size_t)std::max<int64_t>(n, 1)));
-    QEH_TRY(hist.alloc(ctx, (size_t)kRadix * nblocks * 4));
-    QEH_TRY(offs.alloc(ctx, (size_t)kRadix * nblocks * 8));
-    const int ndig = fused ? kPsDig : kRadix;  // digits the histogram holds (digit-major)
-    std::vector<uint32_t> h((size_t)ndig * nblocks, 0);
-    int64_t kept = 0;
-    if (n > 0) {
-        KernelTimer kt(ctx, "partition_move");
-        if (fused) {
-#define QEH_IH(NT)                                                                                                      \
-    hipLaunchKernelGGL(k_ids_hist_pred<NT>, dim3(nblocks), dim3(kRsThreads), 0, ctx->stream, fin, terms, n, seg,      \
-                       (uint32_t)n_parts, ids.as<uint8_t>(), hist.as<uint32_t>(), nblocks)
-            if (terms.n == 0) QEH_IH(0);
-            else if (terms.n == 1) QEH_IH(1);
-            else QEH_IH(2);
-#undef QEH_IH
-        } else {
-            hipLaunchKernelGGL(k_hash_ids8_pred, dim3(grid_for(ctx, n, kBlock * 4, 8)), dim3(kBlock), 0, ctx->stream,
-                               make_colref(kc), cs, terms, n, (uint32_t)n_parts, ids.as<uint8_t>());
-            hipLaunchKernelGGL(k_rs_hist_u8, dim3(nblocks), dim3(kRsThreads), 0, ctx->stream, ids.as<uint8_t>(), n, seg,
-                               hist.as<uint32_t>(), nblocks);  // ids are a byte stream: 16 per load
-        }
-        QEH_HIP(hipGetLastError());
-        QEH_TRY(exclusive_scan_u32(ctx, hist.as<uint32_t>(), offs.as<uint64_t>(), (int64_t)ndig * nblocks, nullptr));
-        QEH_TRY(read_small(ctx, h.data(), hist.p, h.size() * 4));
-        for (int p = 0; p < n_parts; ++p)
-            for (int b = 0; b < nblocks; ++b) counts[p] += h[(size_t)p * nblocks + b];
-        for (int p = 0; p < n_parts; ++p) kept += counts[p];
-    }
-    int made = 0, s = QEH_OK;
-    for (; made < n_move; ++made)
-        if ((s = alloc_column(ctx, cols[move_idx[made]].dtype, kept, false, &out_cols[made])) != QEH_OK) break;
-    if (s == QEH_OK && kept > 0) {
-        PmCols pc{};
-        pc.n = n_move;
-        for (int q = 0; q < n_move; ++q) {
-            const qeh_column &src = cols[move_idx[q]];
-            pc.src[q] = (const uint64_t *)src.values + src.offset;
-            pc.dst[q] = (uint64_t *)out_cols[q].values;
-        }
-        KernelTimer kt(ctx, "partition_move");
-        const bool small = n_parts < kPsDig && !std::getenv("QEH_PM_GENERIC");  // ids 0..n_parts (the drop id)
-#define QEH_FPM(NCV, AT)                                                                                                      \
-    do {                                                                                                               \
-        if (small)                                                                                                     \
-            hipLaunchKernelGGL((k_part_scatter_small<NCV, AT>), dim3(nblocks), dim3(kRsThreads), 0, ctx->stream,             \
-                               ids.as<uint8_t>(), n, seg, offs.as<uint64_t>(), nblocks, pc, (uint32_t)n_parts);        \
-        else                                                                                                           \
-            hipLaunchKernelGGL((k_part_scatter<NCV, AT>), dim3(nblocks), dim3(kRsThreads), 0, ctx->stream, ids.as<uint8_t>(), \
-                               n, seg, offs.as<uint64_t>(), nblocks, pc, (uint32_t)n_parts);                           \
-    } while (0)
-        const bool ballot = rs_ballot(ctx);
-        if (n_move == 1) { if (ballot) QEH_FPM(1, false); else QEH_FPM(1, true); }
-        else if (n_move == 2) { if (ballot) QEH_FPM(2, false); else QEH_FPM(2, true); }
-        else if (n_move == 3) { if (ballot) QEH_FPM(3, false); else QEH_FPM(3, true); }
-        else { if (ballot) QEH_FPM(4, false); else QEH_FPM(4, true); }
-#undef QEH_FPM
-        if (hipGetLastError() != hipSuccess) s = fail(QEH_E_HIP, "filter-partition move launch failed");
-    }
-    if (s == QEH_OK) {
-        const hipError_t e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) s = fail(QEH_E_HIP, std::string("filter-partition move: ") + hipGetErrorString(e));
-    }
-    if (s != QEH_OK)
-        for (int q = 0; q < made; ++q) qeh_column_release(ctx, &out_cols[q]);
-    return s;
-}
-
-extern "C" int qeh_partition_range(qeh_ctx *ctx, const qeh_column *key, const int64_t *boundaries, int n_boundaries,
-                                   int64_t *counts, qeh_column *out_perm) {
-    if (!ctx || !key || !counts || !out_perm || n_boundaries < 0 || n_boundaries >= kRadix ||
-        (n_boundaries > 0 && !boundaries))
-        return fail(QEH_E_INVALID, "qeh_partition_range: bad argument (0..255 boundaries)");
-    DeviceGuard dg(ctx->device);
-    QEH_TRY(check_column(*key, "partition key"));
-    const int64_t n = key->length;
-    DevBuf bd;
-    QEH_TRY(bd.alloc(ctx, (size_t)std::max(n_boundaries, 1) * 8));
-    if (n_boundaries > 0)
-        QEH_HIP(hipMemcpyAsync(bd.p, boundaries, (size_t)n_boundaries * 8, hipMemcpyHostToDevice, ctx->stream));
-    QEH_HIP(hipStreamSynchronize(ctx->stream));
-    const ColRef kc = make_colref(*key);
-    const int is_i64 = key->dtype == QEH_DT_INT64;
-    return partition_perm(
-        ctx, n, n_boundaries + 1,
-        [&](uint64_t *ids, uint32_t *idx) {
-            hipLaunchKernelGGL(k_range_ids_first_below, dim3(grid_for(ctx, n, kBlock * 8, 8)), dim3(kBlock), 0, ctx->stream,
-                               kc, n, bd.as<int64_t>(), n_boundaries, is_i64, ids, idx);
-        },
-        "range_partition", counts, out_perm);
 }
 
 extern "C" int qeh_scatter(qeh_ctx *ctx, const qeh_column *col, const qeh_column *indices, qeh_column *out) {

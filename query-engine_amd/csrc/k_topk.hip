@@ -27,6 +27,7 @@
 
 #include "device_common.h"
 #include "ops.h"
+#include "sort.h"
 
 namespace qeh {
 
@@ -124,7 +125,7 @@ __device__ __forceinline__ uint32_t tk_codes(const TkKey &k, const tk_u32x4 &q, 
     return live;
 }
 
-// lanes of this wave whose digit equals mine (k_sort.hip's digit_peers at this digit width)
+// lanes of this wave whose digit equals mine (radix_device.h's digit_peers at this digit width)
 __device__ __forceinline__ uint64_t tk_peers(uint32_t dg, bool live) {
     uint64_t peers = __ballot(live);
 #pragma unroll
@@ -467,7 +468,7 @@ extern "C" int qeh_sort_indices_limit(qeh_ctx *ctx, const qeh_column *keys, int 
         return qeh_sort_indices_limit(ctx, uk.keys.data(), n_keys, ascending, limit, out_perm);
     }
     int64_t n;
-    QEH_TRY(sort_check_keys(keys, n_keys, &n));
+    QEH_TRY(check_sort_keys(keys, n_keys, &n));
     if (limit == 0 || n == 0) {
         QEH_TRY(alloc_column(ctx, QEH_DT_UINT32, 0, false, out_perm));
         return QEH_OK;

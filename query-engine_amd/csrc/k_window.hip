@@ -2,10 +2,10 @@
 // partitioning instead of a full sort (BASELINE config 5: ROW_NUMBER() OVER (PARTITION BY k
 // ORDER BY v), k in [0, 2^20), 1e9 rows).
 //
-// Semantics as qeh_row_number / qeh_window (k_sort.hip): rows numbered 1.. within each partition
+// Semantics as qeh_row_number / qeh_window (k_window_sort.hip): rows numbered 1.. within each partition
 // in ORDER BY order, ties by input position (docs/WINDOW_FUNCTIONS.md:44-65); RANK with gaps,
 // DENSE_RANK without, NTILE's first size % n buckets one row larger (:67-140); output aligned to
-// input order.  The LSD path of k_sort.hip sorts 40-bit (k, v) pair keys in five 8-bit passes
+// input order.  The LSD path of k_window_sort.hip sorts 40-bit (k, v) pair keys in five 8-bit passes
 // and scatters the numbers back with random 8-B stores; this path moves each row a bounded
 // number of times with run-contiguous writes and no row ids:
 //   1. k_wm_hist1 + k_wm2_pass1: a stable 1024-way partition of (order key, low key bits) by the

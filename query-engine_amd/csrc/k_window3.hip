@@ -2,7 +2,7 @@
 // ORDER BY key, by three levels of 512-way partitioning with whole-chunk writes (BASELINE config 5:
 // ROW_NUMBER() OVER (PARTITION BY k ORDER BY v), k in [0, 2^20), 1e9 rows).
 //
-// Semantics as qeh_row_number / qeh_window (k_sort.hip): rows numbered 1.. within each partition in
+// Semantics as qeh_row_number / qeh_window (k_window_sort.hip): rows numbered 1.. within each partition in
 // ORDER BY order, ties by input position (docs/WINDOW_FUNCTIONS.md:44-65); RANK with gaps, NTILE's
 // first size % n buckets one row larger (:67-140); output aligned to input order.
 //

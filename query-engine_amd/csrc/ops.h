@@ -72,22 +72,6 @@ int columns_minmax_partials(qeh_ctx *ctx, const qeh_column *cols, int n, MinMax 
 int minmax_partials_max_blocks(qeh_ctx *ctx);
 int columns_minmax_collect(qeh_ctx *ctx, const qeh_column *cols, int n, const MinMax *dev_out, int64_t *mn, int64_t *mx,
                            int64_t *valid);
-// Stable sort of (one Int64 / Int32 key, one non-null 8-byte payload) carrying the payload through
-// the radix passes (no gather): the sorted key and payload columns.  kPayloadSortNotEligible when
-// the shapes do not fit (nothing allocated).
-constexpr int kPayloadSortNotEligible = -3;
-int sort_pairs_payload_parts(qeh_ctx *ctx, const qeh_column *keys, const qeh_column *vals, int nparts, bool asc,
-                             bool nulls_first, qeh_column *out_key, qeh_column *out_val);
-int sort_pairs_payload(qeh_ctx *ctx, const qeh_column &key, const qeh_column &val, bool asc, bool nulls_first,
-                       qeh_column *out_key, qeh_column *out_val);
-// What the top-k select (k_topk.hip) needs of the sort (k_sort.hip): qeh_sort_indices' key checks;
-// min / max of a key column's ordered values over its non-NULL rows (mn > mx: none; one synchronous
-// read); and the first min(limit, n) entries of the stable sort permutation of `keys` as a fresh
-// UINT32 column, mapped through rows[] when given (the keys are then those of rows rows[0..n)).
-int sort_check_keys(const qeh_column *keys, int n_keys, int64_t *n);
-int sort_key_range(qeh_ctx *ctx, const qeh_column &col, int64_t *mn, int64_t *mx);
-int sort_perm_prefix(qeh_ctx *ctx, const qeh_column *keys, int n_keys, const int8_t *ascending, int64_t n, int64_t limit,
-                     const uint32_t *rows, qeh_column *out_perm);
 // min / max / valid count of an integer column (one synchronous read).
 int column_minmax(qeh_ctx *ctx, const qeh_column &col, int64_t *mn, int64_t *mx, int64_t *valid);
 // min / max / valid count of several integer columns, one synchronous read.

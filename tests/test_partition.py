@@ -252,3 +252,70 @@ def test_partition_hash_unmove_inverts_move(ctx, n, parts):
     back = ctx.partition_hash_unmove(ctx.upload(k), parts, [moved[1], moved[2]])
     assert np.array_equal(back[0].to_numpy()[0], v)
     assert np.array_equal(back[1].to_numpy()[0], rowid)
+
+
+_SCATTER_ENVS = [None, "QEH_PM_GENERIC", "QEH_RS_BALLOT"]
+_SCATTER_ROWS = [0, 1, 4097, 8193, 40_001]  # around the 4096-row and 8192-row tiles; several ragged segments
+
+
+def _payload(r, n, ncols):
+    """ncols movable (non-null 8-byte) columns, Float64 and Int64 in turn."""
+    return [r.random(n) if c % 2 == 0 else r.integers(-10**9, 10**9, n).astype(np.int64) for c in range(ncols)]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n", _SCATTER_ROWS)
+@pytest.mark.parametrize("parts", [1, 16, 17, 256])  # 16: the last partition count of the small scatter
+@pytest.mark.parametrize("env", _SCATTER_ENVS)
+@pytest.mark.parametrize("ncols", [1, 2, 3, 4])
+def test_partition_hash_move_every_scatter_variant(ctx, monkeypatch, ncols, env, parts, n):
+    """Every (moved columns, ranking, small / 256-digit) variant of the move scatter that
+    qeh_partition_hash_move can launch == qeh_partition_hash's permutation + take, computed under the
+    default environment: same counts, same stable partition-major rows."""
+    import ctypes as C
+    from qe_hip import abi
+    r = np.random.default_rng(1000 * parts + n)
+    k = r.integers(-1000, 1000, n).astype(np.int64)
+    key = ctx.upload(k)
+    cols = [ctx.upload(v) for v in _payload(r, n, ncols)]
+    c2 = (C.c_int64 * parts)()
+    perm = abi.QehColumn()
+    abi.check(ctx.lib.qeh_partition_hash(ctx.h, ctx._cols([key]), 1, parts, c2, C.byref(perm)))
+    perm = ctx._wrap(perm)
+    want = [ctx.take(c, perm).to_numpy()[0] for c in cols]
+    if env:
+        monkeypatch.setenv(env, "1")
+    counts, moved = ctx.partition_hash_move([key], parts, cols)
+    assert list(counts) == list(c2[:]) and counts.sum() == n
+    for m, w in zip(moved, want):
+        got = m.to_numpy()
+        assert got[1] is None and np.array_equal(got[0], w)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n", _SCATTER_ROWS)
+@pytest.mark.parametrize("parts", [1, 15, 16, 255])  # 15: the last small count here (the drop id is one more)
+@pytest.mark.parametrize("env", _SCATTER_ENVS)
+@pytest.mark.parametrize("ncols", [1, 2, 3, 4])
+def test_filter_partition_hash_move_every_scatter_variant(ctx, monkeypatch, ncols, env, parts, n):
+    """The same variants through qeh_filter_partition_hash_move (rejected rows carry the drop id) ==
+    qeh_filter followed by qeh_partition_hash_move, both under the default environment."""
+    from qe_hip import BinaryOp, binop, col, lit
+    r = np.random.default_rng(2000 * parts + n)
+    x = r.integers(0, 100, n).astype(np.int64)
+    w = r.integers(-9, 9, n).astype(np.int64)
+    k = r.integers(-5000, 5000, n).astype(np.int64)
+    cols = [ctx.upload(x), ctx.upload(w), ctx.upload(k)] + [ctx.upload(v) for v in _payload(r, n, ncols)]
+    pred = binop(binop(col(0, "x"), BinaryOp.Greater, lit(49)), BinaryOp.And,
+                 binop(col(1, "w"), BinaryOp.NotEqual, lit(0)))
+    move = list(range(3, 3 + ncols))
+    kept, _ = ctx.filter(cols, pred, out_idx=[2] + move)
+    want_counts, want = ctx.partition_hash_move([kept[0]], parts, kept[1:])
+    want = [c.to_numpy()[0] for c in want]
+    if env:
+        monkeypatch.setenv(env, "1")
+    counts, moved = ctx.filter_partition_hash_move(cols, pred, 2, parts, move)
+    assert list(counts) == list(want_counts)
+    assert counts.sum() == int(((x > 49) & (w != 0)).sum())
+    for m, e in zip(moved, want):
+        assert np.array_equal(m.to_numpy()[0], e)
