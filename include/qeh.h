@@ -60,7 +60,23 @@ enum qeh_dtype {
     QEH_DT_FLOAT32 = 4,
     QEH_DT_FLOAT64 = 5,
     QEH_DT_UTF8 = 6,   /* values = byte buffer, offsets = int32[length+1] */
-    QEH_DT_UINT32 = 7  /* internal: row indices / permutations          */
+    QEH_DT_UINT32 = 7, /* internal: row indices / permutations          */
+    /* Temporal types (types.rs:20-22, :62-66).  Physically Int32 (DATE32: days since 1970-01-01) or
+     * Int64 (DATE64: milliseconds; TIMESTAMP_*: the unit is part of the dtype, so qeh_column keeps
+     * its size).  Arrow formats tdD, tdm, tss:, tsm:, tsu:, tsn:.  A timestamp with a time zone
+     * (tsu:UTC, ...) is refused at import (QEH_E_UNSUPPORTED).  Operators run on the physical
+     * integers; every output that carries an input's values keeps its logical dtype.  Comparisons
+     * need the same temporal dtype on both sides (else QEH_E_TYPE, arrow's "Invalid comparison
+     * operation: Date32 < Int64"); arithmetic, negation and SUM / AVG / MIN / MAX are QEH_E_TYPE
+     * with the reference's messages; COUNT works.  Keys of GROUP BY, ORDER BY, windows, equi-joins
+     * and qeh_in_set may be temporal; keys of qeh_hash_partition, qeh_partition_hash,
+     * qeh_partition_range, qeh_range_partition and qeh_merge_sorted may not (QEH_E_UNSUPPORTED). */
+    QEH_DT_DATE32 = 8,
+    QEH_DT_DATE64 = 9,
+    QEH_DT_TIMESTAMP_S = 10,
+    QEH_DT_TIMESTAMP_MS = 11,
+    QEH_DT_TIMESTAMP_US = 12,
+    QEH_DT_TIMESTAMP_NS = 13
 };
 
 /* An Arrow-layout column.  All pointers are device pointers. */
@@ -709,15 +725,22 @@ int qeh_scatter(qeh_ctx *ctx, const qeh_column *col, const qeh_column *indices, 
  * -1, booleans "t"/"f", integers in decimal, floats as Rust's Display: shortest round-trip
  * digits without exponent, Utf8 bytes).  `out` is an owned Utf8 column whose string i is row
  * i's complete message ('D', Int32 length, Int16 field count, fields), ready to be sent.
- * Types: BOOL, INT32, INT64, UINT32 (as Int64), FLOAT32, FLOAT64, UTF8; <= 32 columns;
- * QEH_E_UNSUPPORTED when the messages exceed 2 GiB (encode the batch in slices). */
+ * Types: BOOL, INT32, INT64, UINT32 (as Int64), FLOAT32, FLOAT64, UTF8 and the temporal types; <= 32
+ * columns; QEH_E_UNSUPPORTED when the messages exceed 2 GiB (encode the batch in slices).
+ * Temporal cells (result.rs:146-172): DATE32 "YYYY-MM-DD" (proleptic Gregorian); DATE64 the date of
+ * ms / 1000 seconds, except that a negative value that is no multiple of 1000 renders as the text
+ * "NULL" (the reference's u32 cast of a negative remainder, result.rs:155-166); TIMESTAMP_*
+ * "YYYY-MM-DDTHH:MM:SS" plus ".fff" / ".ffffff" / ".fffffffff" when the fraction is not zero (chrono's
+ * NaiveDateTime Debug, negative values floored).  A non-NULL date or timestamp whose year lies outside
+ * 0000-9999 is QEH_E_UNSUPPORTED ("... year outside 0000-9999"): encode that batch on the CPU. */
 int qeh_encode_pg_datarows(qeh_ctx *ctx, const qeh_column *cols, int n_cols, qeh_column *out);
 
 /* Arrow IPC stream of one batch (schema message, record batch message, end-of-stream), as
  * SerializedBatch::from_batch writes it with arrow-rs's StreamWriter
  * (crates/query-distributed/src/network.rs:56-72): fields nullable, named `names[i]`, body
  * buffers 64-byte aligned.  Device columns are normalised to offset 0 on the device and copied
- * into a host buffer the library allocates; free it with qeh_host_free. */
+ * into a host buffer the library allocates; free it with qeh_host_free.  DATE32 / DATE64 fields are
+ * flatbuffer Date (unit DAY / MILLISECOND), TIMESTAMP_* fields Timestamp (their unit, no timezone). */
 int qeh_encode_arrow_ipc(qeh_ctx *ctx, const qeh_column *cols, const char *const *names, int n_cols,
                          uint8_t **out_bytes, int64_t *out_size);
 void qeh_host_free(void *p);
@@ -725,8 +748,9 @@ void qeh_host_free(void *p);
 /* The first record batch of an Arrow IPC stream, as SerializedBatch::to_batch reads it
  * (network.rs:75-90), uploaded into owned device columns out_cols[0 .. *out_n_cols); the field
  * names come back NUL-separated in *out_names (free with qeh_host_free; may be NULL).  Int32 /
- * Int64 / UInt32 / Float32 / Float64 / Utf8 / Bool fields; dictionaries, nesting and body
- * compression -> QEH_E_UNSUPPORTED; malformed or truncated input -> QEH_E_INVALID. */
+ * Int64 / UInt32 / Float32 / Float64 / Utf8 / Bool / Date (DAY, MILLISECOND) / Timestamp (any unit)
+ * fields; a Timestamp with a timezone, dictionaries, nesting and body compression ->
+ * QEH_E_UNSUPPORTED; malformed or truncated input -> QEH_E_INVALID. */
 int qeh_decode_arrow_ipc(qeh_ctx *ctx, const uint8_t *bytes, int64_t size, qeh_column *out_cols, int max_cols,
                          int *out_n_cols, char **out_names, int64_t *out_rows);
 

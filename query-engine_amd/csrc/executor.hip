@@ -126,6 +126,13 @@ int dtype_of_format(const char *f, int *dt) {
     else if (!std::strcmp(f, "f")) *dt = QEH_DT_FLOAT32;
     else if (!std::strcmp(f, "b")) *dt = QEH_DT_BOOL;
     else if (!std::strcmp(f, "u")) *dt = QEH_DT_UTF8;
+    else if (!std::strcmp(f, "tdD")) *dt = QEH_DT_DATE32;
+    else if (!std::strcmp(f, "tdm")) *dt = QEH_DT_DATE64;
+    // zone-less timestamps only: "tsu:UTC" and the like fall through to the refusal
+    else if (!std::strcmp(f, "tss:")) *dt = QEH_DT_TIMESTAMP_S;
+    else if (!std::strcmp(f, "tsm:")) *dt = QEH_DT_TIMESTAMP_MS;
+    else if (!std::strcmp(f, "tsu:")) *dt = QEH_DT_TIMESTAMP_US;
+    else if (!std::strcmp(f, "tsn:")) *dt = QEH_DT_TIMESTAMP_NS;
     else return fail(QEH_E_UNSUPPORTED, std::string("arrow type '") + f + "' is not supported on the device");
     return QEH_OK;
 }
@@ -139,6 +146,12 @@ const char *format_of_dtype(int dt) {
         case QEH_DT_BOOL: return "b";
         case QEH_DT_UTF8: return "u";
         case QEH_DT_UINT32: return "I";
+        case QEH_DT_DATE32: return "tdD";
+        case QEH_DT_DATE64: return "tdm";
+        case QEH_DT_TIMESTAMP_S: return "tss:";
+        case QEH_DT_TIMESTAMP_MS: return "tsm:";
+        case QEH_DT_TIMESTAMP_US: return "tsu:";
+        case QEH_DT_TIMESTAMP_NS: return "tsn:";
         default: return "n";
     }
 }
@@ -772,7 +785,7 @@ class Executor {
         }
         node->kind = QEH_EX_LITERAL;
         node->lit_dtype = dt;
-        switch (t->cols[0].c.dtype) {
+        switch (physical_dtype(t->cols[0].c.dtype)) {  // (a temporal value: its integer, lit_dtype keeps the type)
             case QEH_DT_BOOL: node->lit_i64 = (int64_t)bits; break;
             case QEH_DT_INT32: node->lit_i64 = (int64_t)(int32_t)(uint32_t)bits; break;
             case QEH_DT_UINT32: node->lit_i64 = (int64_t)(uint32_t)bits; break;
@@ -1104,9 +1117,11 @@ class Executor {
     }
 
     static bool int_key(const qeh_column &c) { return c.dtype == QEH_DT_INT64 || c.dtype == QEH_DT_INT32; }
-    // two columns a hash join can key on: both integer, or both Utf8 (joined on their shared codes)
+    // two columns a hash join can key on: both integer, both Utf8 (joined on their shared codes), or
+    // both of one temporal type (joined on their physical integers)
     static bool key_pair(const qeh_column &a, const qeh_column &b) {
-        return (int_key(a) && int_key(b)) || (a.dtype == QEH_DT_UTF8 && b.dtype == QEH_DT_UTF8);
+        return (int_key(a) && int_key(b)) || (a.dtype == QEH_DT_UTF8 && b.dtype == QEH_DT_UTF8) ||
+               (is_temporal(a.dtype) && a.dtype == b.dtype);
     }
 
     // The INT32 codes of two Utf8 join key columns from one dictionary built over `build`
@@ -1309,6 +1324,7 @@ class Executor {
             for (size_t j = 0; j < lks.size(); ++j) {
                 lkc.push_back(lc[lks[j]]);
                 rkc.push_back(rc[rks[j]]);
+                if (is_temporal(lkc[j].dtype)) lkc[j] = physical_view(lkc[j]), rkc[j] = physical_view(rkc[j]);
                 if (lkc[j].dtype != QEH_DT_UTF8) continue;
                 Col bc, pc;
                 QEH_TRY(join_codes(rkc[j], lkc[j], &bc, &pc));
@@ -1474,7 +1490,8 @@ class Executor {
             const bool keys_ok = equi_keys(jn->predicate, nl, &lk, &rk);
             const bool pred_left = !pred || (expr_columns(pred) >> nl) == 0;
             // a Utf8 key adds its code column to the probe columns of the one kernel
-            const bool room = !(keys_ok && l.cols[lk].c.dtype == QEH_DT_UTF8) || nl < kMaxCols;
+            // (so does a temporal key: the view of its physical integers)
+            const bool room = !(keys_ok && (l.cols[lk].c.dtype == QEH_DT_UTF8 || is_temporal(l.cols[lk].c.dtype))) || nl < kMaxCols;
             if (keys_ok && room && pred_left && all_columns(nd.exprs, nd.n_exprs, nl, nl + nr) &&
                 all_columns(aexprs.data(), nd.n_aggs, 0, nl) && l.batches > 0 && r.batches > 0) {
                 auto lc = raw(l), rc = raw(r);
@@ -1792,7 +1809,7 @@ class Executor {
                         } else if (lit_f) {
                             return fail(QEH_E_UNSUPPORTED, "LAG/LEAD float default for an integer column");
                         } else {
-                            dflt = adt == QEH_DT_INT32 ? (int64_t)(uint32_t)(int32_t)ln.lit_i64 : ln.lit_i64;
+                            dflt = physical_dtype(adt) == QEH_DT_INT32 ? (int64_t)(uint32_t)(int32_t)ln.lit_i64 : ln.lit_i64;
                         }
                     }
                 }

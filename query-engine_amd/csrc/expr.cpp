@@ -10,6 +10,11 @@
 //   %             -> Int64/Int64 or Int32/Int32, "Modulo operation requires integer arrays" (:711-743)
 //   comparisons   -> coerce_numeric_types (:616-675) then arrow cmp on equal types
 //   AND / OR      -> Boolean only, "AND requires boolean arrays" / "OR ..." (:540-571)
+//   Date32 / Date64 / Timestamp: none of the rules above names them, so they are "unsupported"
+//                    operands of every arithmetic, logical and unary operator; coerce_numeric_types
+//                    leaves them alone, so a comparison needs the same temporal type on both sides
+//                    (arrow's cmp on the physical integers) and any other pairing is arrow's
+//                    "Invalid comparison operation".  The device program carries the physical type.
 //   @@            -> Utf8 on both sides, "@@ left operand must be tsvector (string)" /
 //                    "@@ right operand must be tsquery (string)" (:571-583); TO_TSVECTOR / TO_TSQUERY
 //                    are typed only directly under it (:261-297)
@@ -31,6 +36,13 @@ static const char *dt_name(int t) {
         case QEH_DT_FLOAT64: return "Float64";
         case QEH_DT_UTF8: return "Utf8";
         case QEH_DT_UINT32: return "UInt32";
+        // arrow-rs 53.4.1's Display of the temporal types
+        case QEH_DT_DATE32: return "Date32";
+        case QEH_DT_DATE64: return "Date64";
+        case QEH_DT_TIMESTAMP_S: return "Timestamp(Second, None)";
+        case QEH_DT_TIMESTAMP_MS: return "Timestamp(Millisecond, None)";
+        case QEH_DT_TIMESTAMP_US: return "Timestamp(Microsecond, None)";
+        case QEH_DT_TIMESTAMP_NS: return "Timestamp(Nanosecond, None)";
         default: return "?";
     }
 }
@@ -338,7 +350,7 @@ int compile_expr(const qeh_expr *e, const int32_t *dtypes, int n_cols, DevProgra
                     return fail(QEH_E_UNSUPPORTED, "Utf8 expressions are not evaluated on the device");
                 if ((int)ty.size() >= kNS) return fail(QEH_E_UNSUPPORTED, "expression too deep");
                 in.op = D_LOAD;
-                in.t = (uint8_t)t;
+                in.t = (uint8_t)physical_dtype(t);
                 in.dst = (uint8_t)ty.size();
                 in.a = (uint8_t)nd.index;
                 QEH_TRY(emit(in));
@@ -351,14 +363,14 @@ int compile_expr(const qeh_expr *e, const int32_t *dtypes, int n_cols, DevProgra
                     return fail(QEH_E_UNSUPPORTED, "Utf8 literals are not evaluated on the device");
                 if ((int)ty.size() >= kNS) return fail(QEH_E_UNSUPPORTED, "expression too deep");
                 in.op = D_LIT;
-                in.t = (uint8_t)t;
+                in.t = (uint8_t)physical_dtype(t);  // a temporal literal: a scalar subquery's value
                 in.dst = (uint8_t)ty.size();
                 in.flag = t == QEH_DT_NULL;
                 if (t == QEH_DT_FLOAT64 || t == QEH_DT_FLOAT32) {
                     double d = nd.lit_f64;
                     if (t == QEH_DT_FLOAT32) d = (double)(float)d;
                     in.imm = __builtin_bit_cast(int64_t, d);
-                } else if (t == QEH_DT_INT32) {
+                } else if (physical_dtype(t) == QEH_DT_INT32) {
                     in.imm = (int64_t)(int32_t)nd.lit_i64;
                 } else if (t == QEH_DT_BOOL) {
                     in.imm = nd.lit_i64 != 0;
@@ -418,7 +430,7 @@ int compile_expr(const qeh_expr *e, const int32_t *dtypes, int n_cols, DevProgra
                         in.op = (uint8_t)(D_EQ + (nd.op - QEH_OP_EQ));
                         // Float32 stays Float32 only when both sides are Float32; slots hold
                         // exact doubles, so compare as Float64 either way.
-                        in.t = (uint8_t)(cl == QEH_DT_FLOAT32 ? QEH_DT_FLOAT64 : cl);
+                        in.t = (uint8_t)(cl == QEH_DT_FLOAT32 ? QEH_DT_FLOAT64 : physical_dtype(cl));
                         break;
                     }
                 }

@@ -146,10 +146,11 @@ class FbWriter {
 };
 
 struct IpcType {
-    uint8_t type;       // flatbuffers Type union: Int = 2, FloatingPoint = 3, Utf8 = 5, Bool = 6
+    uint8_t type;       // flatbuffers Type union: Int = 2, FloatingPoint = 3, Utf8 = 5, Bool = 6, Date = 8, Timestamp = 10
     int32_t bit_width;  // Int
     bool is_signed;
-    int16_t precision;  // FloatingPoint: SINGLE = 1, DOUBLE = 2
+    int16_t precision;  // FloatingPoint: SINGLE = 1, DOUBLE = 2; Date: DAY = 0, MILLISECOND = 1;
+                        // Timestamp: SECOND = 0 .. NANOSECOND = 3 (no timezone)
 };
 
 IpcType ipc_type(int dt) {
@@ -161,6 +162,12 @@ IpcType ipc_type(int dt) {
         case QEH_DT_FLOAT32: return {3, 0, false, 1};
         case QEH_DT_FLOAT64: return {3, 0, false, 2};
         case QEH_DT_UTF8: return {5, 0, false, 0};
+        case QEH_DT_DATE32: return {8, 0, false, 0};
+        case QEH_DT_DATE64: return {8, 0, false, 1};
+        case QEH_DT_TIMESTAMP_S: return {10, 0, false, 0};
+        case QEH_DT_TIMESTAMP_MS: return {10, 0, false, 1};
+        case QEH_DT_TIMESTAMP_US: return {10, 0, false, 2};
+        case QEH_DT_TIMESTAMP_NS: return {10, 0, false, 3};
         default: return {0, 0, false, 0};
     }
 }
@@ -211,6 +218,8 @@ void schema_message(FbWriter &w, const qeh_column *cols, const char *const *name
             w.field<int32_t>(ty, 0, t.bit_width);
             w.field<uint8_t>(ty, 1, t.is_signed ? 1 : 0);
         } else if (t.type == 3) {  // FloatingPoint { precision: short }
+            w.field<int16_t>(ty, 0, t.precision);
+        } else if (t.type == 8 || t.type == 10) {  // Date { unit: short }, Timestamp { unit: short, timezone: string (absent) }
             w.field<int16_t>(ty, 0, t.precision);
         }
         w.end_table(ty);
@@ -395,6 +404,20 @@ int dtype_of_ipc(FbReader &r, size_t field, int *dt) {
         }
         case 5: *dt = QEH_DT_UTF8; return QEH_OK;
         case 6: *dt = QEH_DT_BOOL; return QEH_OK;
+        case 8: {  // Date { unit: DateUnit = MILLISECOND }
+            const int16_t u = ty ? r.scalar<int16_t>(ty, 0, 1) : 1;
+            if (u == 0) *dt = QEH_DT_DATE32;
+            else if (u == 1) *dt = QEH_DT_DATE64;
+            else return fail(QEH_E_UNSUPPORTED, "ipc: date unit not supported");
+            return QEH_OK;
+        }
+        case 10: {  // Timestamp { unit: TimeUnit = SECOND, timezone: string }
+            const int16_t u = ty ? r.scalar<int16_t>(ty, 0, 0) : 0;
+            if (ty && r.field(ty, 1)) return fail(QEH_E_UNSUPPORTED, "ipc: timestamps with a time zone are not supported");
+            if (u < 0 || u > 3) return fail(QEH_E_UNSUPPORTED, "ipc: timestamp unit not supported");
+            *dt = QEH_DT_TIMESTAMP_S + u;
+            return QEH_OK;
+        }
         default: return fail(QEH_E_UNSUPPORTED, "ipc: column type not supported");
     }
 }

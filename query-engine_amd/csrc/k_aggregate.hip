@@ -2402,6 +2402,7 @@ static int plan_aggs(const qeh_agg *aggs, int n_aggs, const qeh_column *inputs, 
         s.func = a.func;
         s.col = colset_index[a.column];
         s.in_type = t;
+        // Utf8 and the temporal types are not: operators.rs:764-845 sums and compares numeric arrays only
         const bool numeric = t == QEH_DT_INT32 || t == QEH_DT_INT64 || t == QEH_DT_FLOAT32 || t == QEH_DT_FLOAT64;
         const bool flt = t == QEH_DT_FLOAT32 || t == QEH_DT_FLOAT64;
         switch (a.func) {
@@ -3911,13 +3912,13 @@ static int hash_aggregate_coded(qeh_ctx *ctx, const qeh_column *keys, int n_keys
 }
 
 // Output key columns of an aggregate over dictionary codes back to Utf8 (the NULL group keeps a
-// NULL key); on failure every output column is released.
+// NULL key), and those of temporal keys back to their dtype; on failure every output column is released.
 static int decode_utf8_group_keys(qeh_ctx *ctx, const Utf8Keys &uk, int n_keys, int n_aggs, int status, qeh_column *out_keys,
                                   qeh_column *out_aggs, int64_t *out_groups) {
     if (status != QEH_OK) return status;
     for (int i = 0; i < n_keys; ++i) {
         if (!out_keys[i].values) {  // no column was produced: only its type is the caller's
-            if (uk.dict_of_key[i] >= 0) out_keys[i].dtype = QEH_DT_UTF8;
+            if (uk.dict_of_key[i] >= 0 || is_temporal(uk.logical[i])) out_keys[i].dtype = uk.logical[i];
             continue;
         }
         const int s = uk.decode(i, &out_keys[i]);
@@ -3938,7 +3939,7 @@ int hash_aggregate_filtered(qeh_ctx *ctx, const qeh_column *keys, int n_keys, co
                             int n_inputs, const qeh_agg *aggs, int n_aggs, const qeh_column *pred_cols,
                             int n_pred_cols, const qeh_expr *predicate, int64_t input_batches,
                             qeh_column *out_keys, qeh_column *out_aggs, int64_t *out_groups) {
-    if (!any_utf8(keys, n_keys))
+    if (!any_recoded_key(keys, n_keys))
         return hash_aggregate_coded(ctx, keys, n_keys, agg_inputs, n_inputs, aggs, n_aggs, pred_cols, n_pred_cols, predicate,
                                     input_batches, out_keys, out_aggs, out_groups);
     if (!out_groups) return fail(QEH_E_INVALID, "qeh_hash_aggregate: out_groups is NULL");
@@ -5122,10 +5123,24 @@ extern "C" int qeh_join_filter_aggregate(qeh_ctx *ctx, const qeh_column *probe_c
     QEH_TRY(plan_predicate(predicate, dts.data(), n_probe_cols, &pp));
     AggSpecs specs;
     QEH_TRY(plan_aggs(aggs, n_aggs, probe_cols, n_probe_cols, idx.data(), &specs));
+    if (is_temporal(probe_cols[probe_key_idx].dtype) || is_temporal(build_key->dtype)) {
+        // temporal join keys of one dtype: the join runs on views of their physical integers.  The
+        // probe key's view is appended, so a predicate that reads the key column keeps its typing.
+        if (probe_cols[probe_key_idx].dtype != build_key->dtype)
+            return fail(QEH_E_TYPE, std::string("Invalid argument error: Invalid comparison operation: ") +
+                                        arrow_type_name(probe_cols[probe_key_idx].dtype) + " == " +
+                                        arrow_type_name(build_key->dtype));
+        std::vector<qeh_column> pc(probe_cols, probe_cols + n_probe_cols);
+        pc.push_back(physical_view(probe_cols[probe_key_idx]));
+        const qeh_column bk = physical_view(*build_key);
+        return qeh_join_filter_aggregate(ctx, pc.data(), n_probe_cols + 1, n_probe_cols, predicate, &bk, build_group_keys,
+                                         n_group_keys, aggs, n_aggs, out_keys, out_aggs, out_groups);
+    }
     if (probe_cols[probe_key_idx].dtype != QEH_DT_INT64 && probe_cols[probe_key_idx].dtype != QEH_DT_INT32)
         return fail(QEH_E_UNSUPPORTED, "hash join keys must be Int32/Int64 on the device");
-    if (any_utf8(build_group_keys, n_group_keys)) {
-        // group on the build side's dictionary codes (the arguments are checked above, before the encode)
+    if (any_recoded_key(build_group_keys, n_group_keys)) {
+        // group on the build side's dictionary codes / physical integers (the arguments are checked above,
+        // before the encode)
         if (n_group_keys > kMaxGroupKeys) return fail(QEH_E_UNSUPPORTED, "1..4 group keys supported on the device");
         if (!out_keys || !out_aggs) return fail(QEH_E_INVALID, "qeh_join_filter_aggregate: output columns are NULL");
         for (int i = 0; i < n_group_keys; ++i) out_keys[i] = qeh_column{};

@@ -12,7 +12,7 @@ namespace qeh {
 
 ColRef make_colref(const qeh_column &c) {
     ColRef r{};
-    r.dtype = c.dtype;
+    r.dtype = physical_dtype(c.dtype);  // kernels see Int32 / Int64 for temporal columns
     r.validity = c.validity;
     r.vbit0 = c.offset;
     size_t es = dtype_size(c.dtype);
@@ -28,7 +28,7 @@ int check_column(const qeh_column &c, const char *what) {
     if (c.length > 0 && !c.values) return fail(QEH_E_INVALID, std::string(what) + ": null values pointer");
     if (c.length >= (int64_t)0xFFFFFFFFll)
         return fail(QEH_E_UNSUPPORTED, std::string(what) + ": more than 2^32-1 rows per column");
-    switch (c.dtype) {
+    switch (physical_dtype(c.dtype)) {
         case QEH_DT_BOOL: case QEH_DT_INT32: case QEH_DT_INT64: case QEH_DT_FLOAT32:
         case QEH_DT_FLOAT64: case QEH_DT_UINT32:
             return QEH_OK;
@@ -318,7 +318,7 @@ int gather_column(qeh_ctx *ctx, const qeh_column &src, const uint32_t *idx, int6
     ColRef s = make_colref(src);
     int grid = grid_for(ctx, (m + 63) / 64, kBlock / 64, 8);
     KernelTimer kt(ctx, "gather");
-    switch (src.dtype) {
+    switch (physical_dtype(src.dtype)) {
         case QEH_DT_BOOL:
             hipLaunchKernelGGL(k_gather_bool, dim3(grid), dim3(kBlock), 0, ctx->stream, s, idx, m,
                                (uint64_t *)out->values, (uint64_t *)out->validity);

@@ -453,7 +453,7 @@ static int filter_impl(qeh_ctx *ctx, const qeh_column *cols, int n_cols, const q
         o.src_values = cr.values;
         o.src_valid = cr.validity;
         o.src_vbit0 = cr.vbit0;
-        o.dtype = src.dtype;
+        o.dtype = physical_dtype(src.dtype);
         o.dst_values = out[j].values;
         o.dst_valid = (uint32_t *)out[j].validity;
     }
@@ -639,7 +639,7 @@ extern "C" int qeh_eval(qeh_ctx *ctx, const qeh_column *cols, int n_cols, const 
         KernelTimer kt(ctx, "eval");
         uint32_t *err = (uint32_t *)scr;
         uint64_t *ov = (uint64_t *)out->validity;
-        switch (rt) {
+        switch (physical_dtype(rt)) {
             case QEH_DT_BOOL:
                 hipLaunchKernelGGL(k_eval<3>, dim3(grid), dim3(kBlock), 0, ctx->stream, cs, n_rows, prog, out->values, ov, err);
                 break;

@@ -759,11 +759,32 @@ static int join_materialise_fused(qeh_ctx *ctx, const qeh_column &probe_key, con
 
 using namespace qeh;
 
+// Temporal equi-join keys: both sides must have the same temporal dtype (arrow's cmp takes no other
+// pairing); the join then runs on views of their physical integers.  The payload columns are the
+// caller's, so a temporal key listed among them comes back with its dtype.
+static int temporal_join_keys(const qeh_column &a, const qeh_column &b, qeh_column *va, qeh_column *vb, bool *temporal) {
+    *temporal = is_temporal(a.dtype) || is_temporal(b.dtype);
+    if (!*temporal) return QEH_OK;
+    if (a.dtype != b.dtype)
+        return fail(QEH_E_TYPE, std::string("Invalid argument error: Invalid comparison operation: ") +
+                                    arrow_type_name(a.dtype) + " == " + arrow_type_name(b.dtype));
+    *va = physical_view(a), *vb = physical_view(b);
+    return QEH_OK;
+}
+
 extern "C" int qeh_hash_join_inner(qeh_ctx *ctx, const qeh_column *probe_key, const qeh_column *probe_cols,
                                    int n_probe_cols, const qeh_column *build_key, const qeh_column *build_cols,
                                    int n_build_cols, qeh_column *out_probe, qeh_column *out_build, int64_t *out_rows) {
     if (!ctx || !probe_key || !build_key || !out_rows) return fail(QEH_E_INVALID, "qeh_hash_join_inner: bad argument");
     *out_rows = 0;
+    {
+        qeh_column vp, vb;
+        bool temporal;
+        QEH_TRY(temporal_join_keys(*probe_key, *build_key, &vp, &vb, &temporal));
+        if (temporal)
+            return qeh_hash_join_inner(ctx, &vp, probe_cols, n_probe_cols, &vb, build_cols, n_build_cols, out_probe, out_build,
+                                       out_rows);
+    }
     DeviceGuard dg(ctx->device);
     QEH_TRY(check_column(*probe_key, "probe key"));
     if (probe_key->dtype != QEH_DT_INT64 && probe_key->dtype != QEH_DT_INT32)
@@ -1016,6 +1037,14 @@ extern "C" int qeh_hash_join_outer(qeh_ctx *ctx, int join_type, const qeh_column
         (n_right_cols > 0 && (!right_cols || !out_right)))
         return fail(QEH_E_INVALID, "qeh_hash_join_outer: bad argument");
     *out_rows = 0;
+    {
+        qeh_column vl, vr;
+        bool temporal;
+        QEH_TRY(temporal_join_keys(*left_key, *right_key, &vl, &vr, &temporal));
+        if (temporal)
+            return qeh_hash_join_outer(ctx, join_type, &vl, left_cols, n_left_cols, &vr, right_cols, n_right_cols, out_left,
+                                       out_right, out_rows);
+    }
     if (join_type == 0)
         return qeh_hash_join_inner(ctx, left_key, left_cols, n_left_cols, right_key, right_cols, n_right_cols, out_left,
                                    out_right, out_rows);
@@ -1235,7 +1264,7 @@ extern "C" int qeh_hash_join(qeh_ctx *ctx, int join_type, const qeh_column *left
     if (!ctx || !left_key || !right_key || !out_rows) return fail(QEH_E_INVALID, "qeh_hash_join: bad argument");
     *out_rows = 0;
     const bool lu = left_key->dtype == QEH_DT_UTF8, ru = right_key->dtype == QEH_DT_UTF8;
-    if (lu != ru)
+    if (lu != ru || ((is_temporal(left_key->dtype) || is_temporal(right_key->dtype)) && left_key->dtype != right_key->dtype))
         return fail(QEH_E_TYPE, std::string("Invalid argument error: Invalid comparison operation: ") +
                                     arrow_type_name(left_key->dtype) + " == " + arrow_type_name(right_key->dtype));
     if (!lu)

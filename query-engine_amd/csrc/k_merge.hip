@@ -169,6 +169,10 @@ extern "C" int qeh_merge_sorted(qeh_ctx *ctx, const qeh_column *parts, int n_par
     if (n_parts == 0) return fail(QEH_E_INVALID, "qeh_merge_sorted: no partitions (the reference returns no batches)");
     for (int k = 0; k < n_keys; ++k)
         if (key_idx[k] < 0 || key_idx[k] >= n_cols) return fail(QEH_E_INVALID, "qeh_merge_sorted: sort column out of range");
+    for (int k = 0; k < n_keys; ++k)
+        for (int p = 0; p < n_parts; ++p)
+            if (is_temporal(parts[(size_t)p * n_cols + key_idx[k]].dtype))
+                return fail(QEH_E_UNSUPPORTED, "temporal merge keys are not supported on the device");
     DeviceGuard dg(ctx->device);
     if (n_keys == 1 && n_cols == 2 && n_parts <= 16) {
         // one key and one 8-byte payload: the payload rides through the radix passes (no gathers), and the

@@ -628,6 +628,7 @@ extern "C" int qeh_range_partition(qeh_ctx *ctx, const qeh_column *key, int asce
     DeviceGuard dg(ctx->device);
     QEH_TRY(check_column(*key, "partition key"));
     if (key->dtype == QEH_DT_UTF8) return fail(QEH_E_UNSUPPORTED, "Utf8 range partition keys are not supported on the device");
+    if (is_temporal(key->dtype)) return fail(QEH_E_UNSUPPORTED, "temporal range partition keys are not supported on the device");
     for (int j = 1; j < n_splitters; ++j)
         if (splitters[j] < splitters[j - 1]) return fail(QEH_E_INVALID, "qeh_range_partition: splitters must be ascending");
     const int64_t n = key->length;
@@ -807,8 +808,9 @@ extern "C" int qeh_partition_hash_move(qeh_ctx *ctx, const qeh_column *keys, int
         QEH_TRY(check_column(cols[c], "partition column"));
         if (cols[c].length != n) return fail(QEH_E_INVALID, "partition columns and keys have different lengths");
     }
-    auto movable = [](const qeh_column &c) {
-        return (c.dtype == QEH_DT_INT64 || c.dtype == QEH_DT_FLOAT64) && (!c.validity || c.null_count == 0);
+    auto movable = [](const qeh_column &c) {  // 8-byte values (Date64 / timestamps are Int64), moved as they are
+        const int pt = physical_dtype(c.dtype);
+        return (pt == QEH_DT_INT64 || pt == QEH_DT_FLOAT64) && (!c.validity || c.null_count == 0);
     };
     std::vector<int32_t> mv, other;
     for (int c = 0; c < n_cols; ++c) (movable(cols[c]) ? mv : other).push_back(c);
@@ -987,6 +989,7 @@ extern "C" int qeh_partition_range(qeh_ctx *ctx, const qeh_column *key, const in
         return fail(QEH_E_INVALID, "qeh_partition_range: bad argument (0..255 boundaries)");
     DeviceGuard dg(ctx->device);
     QEH_TRY(check_column(*key, "partition key"));
+    if (is_temporal(key->dtype)) return fail(QEH_E_UNSUPPORTED, "temporal range partition keys are not supported on the device");
     const int64_t n = key->length;
     DevBuf bd;
     QEH_TRY(bd.alloc(ctx, (size_t)std::max(n_boundaries, 1) * 8));

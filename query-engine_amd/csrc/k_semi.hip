@@ -360,6 +360,8 @@ int in_set(qeh_ctx *ctx, const qeh_column &probe, const qeh_column &set, int neg
     std::memset(out, 0, sizeof(*out));
     QEH_TRY(check_column(probe, "in_set probe"));
     QEH_TRY(check_column(set, "in_set set"));
+    if (probe.dtype == set.dtype && is_temporal(probe.dtype))  // the same temporal type: its physical integers
+        return in_set(ctx, physical_view(probe), physical_view(set), negated, out);
     const int pt = probe.dtype, st = set.dtype;
     const bool ints = semi_int(pt) && semi_int(st);
     const bool floats = pt == st && (pt == QEH_DT_FLOAT32 || pt == QEH_DT_FLOAT64);

@@ -894,7 +894,7 @@ using namespace qeh;
 static int sort_indices(qeh_ctx *ctx, const qeh_column *keys, int n_keys, const int8_t *ascending, const int8_t *nulls_first,
                         qeh_column *out_perm) {
     DeviceGuard dg(ctx->device);
-    if (any_utf8(keys, n_keys)) {  // codes compare as the strings do
+    if (any_recoded_key(keys, n_keys)) {  // codes compare as the strings do; temporal keys as their integers
         Utf8Keys uk;
         QEH_TRY(encode_utf8_keys(ctx, keys, n_keys, &uk));
         return sort_indices(ctx, uk.keys.data(), n_keys, ascending, nulls_first, out_perm);
@@ -1575,7 +1575,7 @@ extern "C" int qeh_scatter(qeh_ctx *ctx, const qeh_column *col, const qeh_column
     if (indices->length != col->length) return fail(QEH_E_INVALID, "scatter: indices and column lengths differ");
     if (col->validity && col->null_count != 0) return fail(QEH_E_UNSUPPORTED, "scatter: nullable columns");
     int w = 0;
-    switch (col->dtype) {
+    switch (physical_dtype(col->dtype)) {
         case QEH_DT_INT64: case QEH_DT_FLOAT64: w = 8; break;
         case QEH_DT_INT32: case QEH_DT_FLOAT32: case QEH_DT_UINT32: w = 4; break;
         default: return fail(QEH_E_UNSUPPORTED, "scatter: fixed-width numeric columns only");

@@ -462,7 +462,7 @@ extern "C" int qeh_sort_indices_limit(qeh_ctx *ctx, const qeh_column *keys, int 
     if (!ctx || !keys || !out_perm) return fail(QEH_E_INVALID, "qeh_sort_indices_limit: bad argument");
     if (limit < 0) return fail(QEH_E_INVALID, "qeh_sort_indices_limit: negative limit");
     DeviceGuard dg(ctx->device);
-    if (any_utf8(keys, n_keys)) {  // codes compare as the strings do
+    if (any_recoded_key(keys, n_keys)) {  // codes compare as the strings do; temporal keys as their integers
         Utf8Keys uk;
         QEH_TRY(encode_utf8_keys(ctx, keys, n_keys, &uk));
         return qeh_sort_indices_limit(ctx, uk.keys.data(), n_keys, ascending, limit, out_perm);

@@ -96,6 +96,12 @@ const char *arrow_type_name(int dt) {
         case QEH_DT_FLOAT64: return "Float64";
         case QEH_DT_UTF8: return "Utf8";
         case QEH_DT_UINT32: return "UInt32";
+        case QEH_DT_DATE32: return "Date32";
+        case QEH_DT_DATE64: return "Date64";
+        case QEH_DT_TIMESTAMP_S: return "Timestamp(Second, None)";
+        case QEH_DT_TIMESTAMP_MS: return "Timestamp(Millisecond, None)";
+        case QEH_DT_TIMESTAMP_US: return "Timestamp(Microsecond, None)";
+        case QEH_DT_TIMESTAMP_NS: return "Timestamp(Nanosecond, None)";
         default: return "?";
     }
 }

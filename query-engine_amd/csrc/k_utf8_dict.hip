@@ -621,7 +621,10 @@ int encode_utf8_keys(qeh_ctx *ctx, const qeh_column *keys, int n_keys, Utf8Keys 
     out->ctx = ctx;
     out->keys.assign(keys, keys + std::max(n_keys, 0));
     out->dict_of_key.assign((size_t)std::max(n_keys, 0), -1);
+    out->logical.assign((size_t)std::max(n_keys, 0), 0);
     for (int i = 0; i < n_keys; ++i) {
+        out->logical[i] = keys[i].dtype;
+        if (is_temporal(keys[i].dtype)) out->keys[i] = physical_view(keys[i]);
         if (keys[i].dtype != QEH_DT_UTF8) continue;
         qeh_column codes{}, dict{};
         QEH_TRY(utf8_dict_encode(ctx, keys[i], &codes, &dict));
@@ -635,7 +638,9 @@ int encode_utf8_keys(qeh_ctx *ctx, const qeh_column *keys, int n_keys, Utf8Keys 
 }
 
 int Utf8Keys::decode(int key, qeh_column *col) const {
-    if (key < 0 || key >= (int)dict_of_key.size() || dict_of_key[key] < 0) return QEH_OK;
+    if (key < 0 || key >= (int)dict_of_key.size()) return QEH_OK;
+    if (is_temporal(logical[key]) && col->dtype == physical_dtype(logical[key])) col->dtype = logical[key];
+    if (dict_of_key[key] < 0) return QEH_OK;
     const qeh_column &dict = dicts[dict_of_key[key]];
     const int64_t g = col->length;
     DevBuf idx;

@@ -206,7 +206,8 @@ __global__ void k_rn_scatter_xcd(const uint32_t *__restrict__ dst, const uint32_
 using namespace qeh;
 
 // The sort keys of a window: the PARTITION BY keys (ascending), then the ORDER BY keys as given.
-// Utf8 keys are replaced by their dictionary codes, which compare as the strings do.
+// Utf8 keys are replaced by their dictionary codes, which compare as the strings do, temporal keys
+// by views of their physical integers.
 struct WindowKeys {
     Utf8Keys pk, ok;                  // own the codes
     const qeh_column *part, *order;   // the keys to use: the caller's, or pk's / ok's
@@ -217,7 +218,7 @@ struct WindowKeys {
 static int make_window_keys(qeh_ctx *ctx, const qeh_column *part_keys, int n_part, const qeh_column *order_keys, int n_order,
                             const int8_t *ascending, WindowKeys *w) {
     w->part = part_keys, w->order = order_keys;
-    if (any_utf8(part_keys, n_part) || any_utf8(order_keys, n_order)) {
+    if (any_recoded_key(part_keys, n_part) || any_recoded_key(order_keys, n_order)) {
         QEH_TRY(encode_utf8_keys(ctx, part_keys, n_part, &w->pk));
         QEH_TRY(encode_utf8_keys(ctx, order_keys, n_order, &w->ok));
         w->part = w->pk.keys.data(), w->order = w->ok.keys.data();
@@ -457,6 +458,12 @@ extern "C" int qeh_window(qeh_ctx *ctx, int32_t func, const qeh_column *part_key
     const bool value_fn = func >= QEH_WIN_LAG;
     if (func == QEH_WIN_NTILE && param < 1) return fail(QEH_E_INVALID, "NTILE needs a bucket count >= 1");
     if ((func == QEH_WIN_LAG || func == QEH_WIN_LEAD) && param < 0) return fail(QEH_E_INVALID, "LAG/LEAD offset must be >= 0");
+    if (arg && is_temporal(arg->dtype)) {  // the values move as their physical integers and keep their dtype
+        const qeh_column pa = physical_view(*arg);
+        QEH_TRY(qeh_window(ctx, func, part_keys, n_part, order_keys, n_order, ascending, &pa, param, dflt, out));
+        if (value_fn) out->dtype = arg->dtype;
+        return QEH_OK;
+    }
     int esz = 8;
     if (value_fn) {
         if (!arg) return fail(QEH_E_INVALID, "window value function needs an argument column");

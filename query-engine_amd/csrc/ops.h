@@ -185,12 +185,14 @@ int ts_match(qeh_ctx *ctx, const TsSide &doc, const TsSide &query, int64_t n, qe
 // its INT32 order-preserving dictionary codes (each Utf8 column gets its own dictionary), so the
 // integer sort / group / window paths take it.  Owns the code and dictionary columns.  decode()
 // turns an operator's output code column for key `key` back into a Utf8 column (NULL stays NULL);
-// a key that was not Utf8 is left alone.
+// a key that was not Utf8 is left alone.  Temporal key columns are replaced by views with their
+// physical integer dtype (no copy), and decode() gives such an output column its logical dtype back.
 struct Utf8Keys {
     qeh_ctx *ctx = nullptr;
     std::vector<qeh_column> keys;
     std::vector<qeh_column> codes, dicts;
     std::vector<int> dict_of_key;
+    std::vector<int32_t> logical;  // dtype of each input key
     Utf8Keys() = default;
     Utf8Keys(const Utf8Keys &) = delete;
     Utf8Keys &operator=(const Utf8Keys &) = delete;
@@ -213,6 +215,13 @@ inline bool any_utf8(const qeh_column *cols, int n) {
         if (cols[i].dtype == QEH_DT_UTF8) return true;
     return false;
 }
+inline bool any_temporal(const qeh_column *cols, int n) {
+    for (int i = 0; cols && i < n; ++i)
+        if (is_temporal(cols[i].dtype)) return true;
+    return false;
+}
+// key columns that encode_utf8_keys has to replace before the integer paths take them
+inline bool any_recoded_key(const qeh_column *cols, int n) { return any_utf8(cols, n) || any_temporal(cols, n); }
 
 // Window functions over one bounded integer PARTITION BY key and one ORDER BY key by partitioning
 // (k_window.hip): ROW_NUMBER / RANK / DENSE_RANK / NTILE into a fresh Int64 column.

@@ -192,6 +192,21 @@ inline int grid_for(qeh_ctx *ctx, int64_t work_items, int items_per_block, int p
     return (int)want;
 }
 
+// Temporal dtypes are stored as integers: every kernel runs on the physical type, and launch
+// sites switch on physical_dtype(dt) where they pick a kernel by dtype.
+inline bool is_temporal(int dt) { return dt >= QEH_DT_DATE32 && dt <= QEH_DT_TIMESTAMP_NS; }
+inline int physical_dtype(int dt) {
+    if (dt == QEH_DT_DATE32) return QEH_DT_INT32;
+    return is_temporal(dt) ? QEH_DT_INT64 : dt;
+}
+// `c` with its physical dtype (a view: same buffers, not owned)
+inline qeh_column physical_view(const qeh_column &c) {
+    qeh_column v = c;
+    v.dtype = physical_dtype(c.dtype);
+    v.owned = 0;
+    return v;
+}
+
 size_t dtype_size(int dt);
 int alloc_column(qeh_ctx *ctx, int dtype, int64_t length, bool with_validity, qeh_column *out);
 

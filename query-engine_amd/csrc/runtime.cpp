@@ -151,7 +151,7 @@ int scratch_zeroed(qeh_ctx *ctx, size_t bytes, void **out) {
 }
 
 size_t dtype_size(int dt) {
-    switch (dt) {
+    switch (physical_dtype(dt)) {
         case QEH_DT_INT32: return 4;
         case QEH_DT_UINT32: return 4;
         case QEH_DT_FLOAT32: return 4;

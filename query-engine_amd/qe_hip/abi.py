@@ -19,6 +19,16 @@ STATUS_NAMES = {0: "OK", 1: "INVALID", 2: "OVERFLOW", 3: "DIV0", 4: "OOM", 5: "U
                 6: "HIP", 7: "TYPE", 8: "INTERNAL"}
 
 DT_NULL, DT_BOOL, DT_INT32, DT_INT64, DT_FLOAT32, DT_FLOAT64, DT_UTF8, DT_UINT32 = range(8)
+# temporal types: physically Int32 (DATE32) / Int64 (the rest); the timestamp unit is part of the dtype
+DT_DATE32, DT_DATE64, DT_TIMESTAMP_S, DT_TIMESTAMP_MS, DT_TIMESTAMP_US, DT_TIMESTAMP_NS = range(8, 14)
+TEMPORAL_DTYPES = frozenset(range(8, 14))
+
+
+def physical_dtype(dt: int) -> int:
+    """The integer type a temporal dtype is stored as; every other dtype is its own."""
+    if dt == DT_DATE32:
+        return DT_INT32
+    return DT_INT64 if dt in TEMPORAL_DTYPES else dt
 
 EX_COLUMN, EX_LITERAL, EX_BINARY, EX_UNARY = 1, 2, 3, 4
 EX_SCALAR_SUBQUERY, EX_IN_SUBQUERY, EX_EXISTS = 5, 6, 7

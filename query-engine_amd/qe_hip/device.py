@@ -20,6 +20,34 @@ NP_OF = {abi.DT_INT32: np.int32, abi.DT_INT64: np.int64, abi.DT_FLOAT32: np.floa
 DT_OF = {np.dtype(np.int32): abi.DT_INT32, np.dtype(np.int64): abi.DT_INT64,
          np.dtype(np.float32): abi.DT_FLOAT32, np.dtype(np.float64): abi.DT_FLOAT64,
          np.dtype(np.uint32): abi.DT_UINT32, np.dtype(np.bool_): abi.DT_BOOL}
+# temporal dtypes <-> numpy datetime64 units.  Date32 holds Int32 days and Date64 Int64 milliseconds;
+# numpy has one day type and no second millisecond type, so datetime64[D] uploads as Date32 and
+# datetime64[ms] as Timestamp(ms): pass ``dtype=abi.DT_DATE64`` to upload() for a Date64 column.
+NP_UNIT_OF = {abi.DT_DATE32: "D", abi.DT_DATE64: "ms", abi.DT_TIMESTAMP_S: "s", abi.DT_TIMESTAMP_MS: "ms",
+              abi.DT_TIMESTAMP_US: "us", abi.DT_TIMESTAMP_NS: "ns"}
+DT_OF_NP_UNIT = {"D": abi.DT_DATE32, "s": abi.DT_TIMESTAMP_S, "ms": abi.DT_TIMESTAMP_MS,
+                 "us": abi.DT_TIMESTAMP_US, "ns": abi.DT_TIMESTAMP_NS}
+
+
+def arrow_type_of(dt: int):
+    """The pyarrow DataType of a qeh dtype (temporal types keep their unit; no time zones)."""
+    import pyarrow as pa
+    return {abi.DT_BOOL: pa.bool_(), abi.DT_INT32: pa.int32(), abi.DT_INT64: pa.int64(), abi.DT_FLOAT32: pa.float32(),
+            abi.DT_FLOAT64: pa.float64(), abi.DT_UTF8: pa.string(), abi.DT_UINT32: pa.uint32(),
+            abi.DT_DATE32: pa.date32(), abi.DT_DATE64: pa.date64(), abi.DT_TIMESTAMP_S: pa.timestamp("s"),
+            abi.DT_TIMESTAMP_MS: pa.timestamp("ms"), abi.DT_TIMESTAMP_US: pa.timestamp("us"),
+            abi.DT_TIMESTAMP_NS: pa.timestamp("ns")}[dt]
+
+
+def dtype_of_arrow(t) -> int:
+    """The qeh dtype of a pyarrow DataType; a timestamp with a time zone and every other type the
+    device does not hold raise TypeError."""
+    for dt in (abi.DT_BOOL, abi.DT_INT32, abi.DT_INT64, abi.DT_FLOAT32, abi.DT_FLOAT64, abi.DT_UTF8, abi.DT_UINT32,
+               abi.DT_DATE32, abi.DT_DATE64, abi.DT_TIMESTAMP_S, abi.DT_TIMESTAMP_MS, abi.DT_TIMESTAMP_US,
+               abi.DT_TIMESTAMP_NS):
+        if t == arrow_type_of(dt):
+            return dt
+    raise TypeError(f"arrow type {t} is not supported on the device")
 
 
 def pack_bits(b: np.ndarray) -> np.ndarray:
@@ -107,11 +135,26 @@ class DeviceColumn:
             if n > 0:
                 ctx.d2h(vb, self.c.values, nbytes)
             return unpack_bits(vb, n, off), valid
-        npdt = NP_OF[self.c.dtype]
+        npdt = NP_OF[abi.physical_dtype(self.c.dtype)]
         out = np.empty(n, npdt)
         if n > 0:
             ctx.d2h(out, self.c.values + off * out.itemsize, n * out.itemsize)
+        if self.c.dtype in abi.TEMPORAL_DTYPES:  # the integers as datetime64 of the dtype's unit
+            out = out.astype(np.int64).view(f"datetime64[{NP_UNIT_OF[self.c.dtype]}]")
         return out, valid
+
+    def to_arrow(self):
+        """The column as a pyarrow array of its own DataType (Date32, Timestamp(us), ...)."""
+        import pyarrow as pa
+        values, valid = self.to_numpy()
+        mask = None if valid is None else ~valid
+        dt = self.c.dtype
+        if dt == abi.DT_UTF8:
+            return pa.array(list(values), type=pa.string(), mask=mask)
+        if dt in abi.TEMPORAL_DTYPES:
+            phys = values.view(np.int64).astype(NP_OF[abi.physical_dtype(dt)])
+            return pa.array(phys, mask=mask).view(arrow_type_of(dt))
+        return pa.array(values, type=arrow_type_of(dt), mask=mask)
 
 
 class Context:
@@ -177,14 +220,27 @@ class Context:
         return ms.value, n.value
 
     # ---- columns ---------------------------------------------------------
-    def upload(self, values: np.ndarray, valid: Optional[np.ndarray] = None, offset: int = 0) -> DeviceColumn:
+    def upload(self, values: np.ndarray, valid: Optional[np.ndarray] = None, offset: int = 0,
+               dtype: Optional[int] = None) -> DeviceColumn:
         """numpy -> Arrow-layout device column.  `offset` prepends that many
         padding rows and records them as the Arrow array offset (exercises
-        non-zero offsets)."""
+        non-zero offsets).  datetime64[D] becomes Date32, datetime64[s|ms|us|ns] the Timestamp of
+        that unit; `dtype` = a temporal abi.DT_* gives integers (or datetime64 values) that type."""
         if isinstance(values, (list, tuple)) or (isinstance(values, np.ndarray) and values.dtype == object):
             return self._upload_utf8(list(values), valid)
         values = np.asarray(values)
-        dt = DT_OF.get(values.dtype)
+        if values.dtype.kind == "M":
+            unit = np.datetime_data(values.dtype)[0]
+            if dtype is None:
+                dtype = DT_OF_NP_UNIT.get(unit)
+            if dtype not in abi.TEMPORAL_DTYPES:
+                raise TypeError(f"unsupported dtype {values.dtype}")
+            values = values.astype(f"datetime64[{NP_UNIT_OF[dtype]}]").view(np.int64)
+        if dtype is not None:
+            if dtype not in abi.TEMPORAL_DTYPES or values.dtype.kind != "i":
+                raise TypeError("upload(dtype=...) takes a temporal dtype over integer or datetime64 values")
+            values = values.astype(NP_OF[abi.physical_dtype(dtype)])
+        dt = dtype if dtype is not None else DT_OF.get(values.dtype)
         if dt is None:
             raise TypeError(f"unsupported dtype {values.dtype}")
         n = len(values)
@@ -208,6 +264,23 @@ class Context:
             c.validity = q
             c.null_count = int(n - valid.sum())
         return DeviceColumn(self, c, bufs)
+
+    def upload_arrow(self, arr, offset: int = 0) -> DeviceColumn:
+        """pyarrow array (or chunked array) -> device column of the same DataType."""
+        import pyarrow as pa
+        if isinstance(arr, pa.ChunkedArray):
+            arr = arr.combine_chunks()
+        dt = dtype_of_arrow(arr.type)
+        valid = None if arr.null_count == 0 else ~np.asarray(arr.is_null())
+        if dt == abi.DT_UTF8:
+            return self._upload_utf8(arr.to_pylist(), valid)
+        if dt in abi.TEMPORAL_DTYPES:
+            arr = arr.view(arrow_type_of(abi.physical_dtype(dt)))
+        if dt == abi.DT_BOOL:
+            values = np.asarray(arr.fill_null(False))
+        else:
+            values = arr.fill_null(0).to_numpy(zero_copy_only=False)
+        return self.upload(values, valid, offset, dtype=dt if dt in abi.TEMPORAL_DTYPES else None)
 
     def _upload_utf8(self, strs, valid=None) -> DeviceColumn:
         n = len(strs)
@@ -233,7 +306,7 @@ class Context:
 
     def empty(self, dtype: int, n: int) -> DeviceColumn:
         """Uninitialised device column (no validity) from the pool."""
-        item = np.dtype(NP_OF[dtype]).itemsize
+        item = np.dtype(NP_OF[abi.physical_dtype(dtype)]).itemsize
         p = self.alloc(max(n * item, 8))
         c = abi.QehColumn(dtype=dtype, owned=0, length=n, offset=0, null_count=0, values=p)
         return DeviceColumn(self, c, [p])
@@ -809,7 +882,7 @@ class Context:
         d = None
         if default is not None:
             dt = {abi.DT_INT32: np.int32, abi.DT_INT64: np.int64, abi.DT_FLOAT32: np.float32,
-                  abi.DT_FLOAT64: np.float64}[arg.c.dtype]
+                  abi.DT_FLOAT64: np.float64}[abi.physical_dtype(arg.c.dtype)]
             bits = np.zeros(1, np.int64)
             if np.dtype(dt).itemsize == 8:
                 bits.view(dt)[0] = default

@@ -232,6 +232,8 @@ class DistributedExecutor:
         """Column -> payload tensors: values (Boolean: a byte per row; Utf8: int32 lengths, then
         the bytes), then validity bytes when the column has a bitmap."""
         n = len(col)
+        if col.dtype in abi.TEMPORAL_DTYPES:  # the partitioner's rules for these types are not ported yet
+            raise abi.QehError(abi.QEH_E_UNSUPPORTED, "temporal columns are not supported by the distributed layer")
         if col.dtype in (abi.DT_UTF8, abi.DT_BOOL):
             if self.device == "cuda":
                 if col.dtype == abi.DT_BOOL:

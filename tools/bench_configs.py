@@ -38,7 +38,7 @@
 
 Prints one JSON line per config: rows/s, ms per run, algorithmic GB/s and
 fraction of 8 TB/s, and the oracle's rows/s on a bounded sample (1 thread).
-usage: python tools/bench_configs.py [--only cfg2,cfg3,cfg5,window,filter,limit,plan,left,full,merge,encode,partition,utf8_groupby,utf8_sort,utf8_join,topk,semi,tsmatch] [--scale 1.0]
+usage: python tools/bench_configs.py [--only cfg2,cfg3,cfg5,window,filter,limit,plan,left,full,merge,encode,partition,utf8_groupby,utf8_sort,utf8_join,topk,semi,tsmatch,temporal] [--scale 1.0]
 """
 import argparse
 import json
@@ -1031,6 +1031,52 @@ def cfg_tsmatch(ctx, scale):
           "true_share_of_first_block_on_host": sample / len(docs), "both_kernels_agree": selected["stream"] == selected["rows"]})
 
 
+def cfg_temporal(ctx, scale):
+    """pgwire DataRow text of 1e7 rows x (Int64, Date32, Timestamp(us)) against the same call over three
+    Int64 columns (the path these columns' values took before they had a type), interleaved in this
+    process: one warm-up and 5 timed calls each, medians, kernel times by name, and the ratio per
+    output byte.  The dates cover years 1900-2100, half the timestamps carry a microsecond fraction."""
+    n = int(1e7 * scale)
+    r = np.random.default_rng(SEED)
+    k = ctx.generate(abi.GEN_UNIFORM_MOD, SEED, 2, n, 1 << 40)
+    days = r.integers(-25567, 47482, n).astype(np.int32)
+    us = r.integers(-25567 * 86400, 47482 * 86400, n) * 10 ** 6 + np.where(r.random(n) < 0.5, 0, r.integers(0, 10 ** 6, n))
+    d32, tsu = ctx.upload(days, dtype=abi.DT_DATE32), ctx.upload(us, dtype=abi.DT_TIMESTAMP_US)
+    sides = {"temporal": [k, d32, tsu], "int64": [k, ctx.upload(days.astype(np.int64)), ctx.upload(us)]}
+    kernels = ["encode_len", "encode_write"]
+    wall = {s: [] for s in sides}
+    kms = {s: {kn: [] for kn in kernels} for s in sides}
+    nbytes = {}
+    ctx.timing(True)
+    for it in range(6):  # the first round warms both sides up
+        for side, cols in sides.items():
+            ctx.timing_reset()
+            ctx.sync()
+            t0 = time.perf_counter()
+            out = ctx.encode_pg_datarows(cols)
+            ctx.sync()
+            dt = time.perf_counter() - t0
+            nbytes[side] = out.c.values_bytes
+            out.release()
+            if it:
+                wall[side].append(dt * 1e3)
+                for kn in kernels:
+                    kms[side][kn].append(ctx.kernel_time(kn)[0])
+    ctx.timing(False)
+    res = {}
+    for side in sides:
+        med = {kn: float(np.median(v)) for kn, v in kms[side].items()}
+        res[side] = {"wall_ms_median": float(np.median(wall[side])), "kernels_ms_median": med,
+                     "kernel_ms": sum(med.values()), "encoded_bytes": nbytes[side],
+                     "kernel_ns_per_output_byte": sum(med.values()) * 1e6 / nbytes[side]}
+    t, i = res["temporal"], res["int64"]
+    in_bytes = 20.0 * n
+    line(f"pgwire DataRow text encoding {n} x (Int64, Date32, Timestamp(us)) vs 3 x Int64", n, t["wall_ms_median"] * 1e-3,
+         in_bytes + t["encoded_bytes"], t["kernel_ms"], "k_pg_row_len + k_pg_row_write (civil date from days)", None,
+         {"temporal": t, "int64": i, "kernel_ratio_temporal_over_int64": t["kernel_ms"] / i["kernel_ms"],
+          "per_output_byte_ratio": t["kernel_ns_per_output_byte"] / i["kernel_ns_per_output_byte"]})
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--only", default="cfg2,cfg3,cfg5,filter")
@@ -1047,7 +1093,7 @@ def main():
          "merge": cfg_merge, "encode": cfg_encode, "shapes": cfg_metric_shapes, "partition": cfg_partition, "cfg3w": cfg3_wide, "window": cfg_window,
          "cfg4leg": cfg4_leg, "cfg4items": cfg4_items_leg, "cfg5leg": cfg5_leg,
          "window_lsd": cfg_window_lsd, "utf8_groupby": cfg_utf8_groupby, "utf8_sort": cfg_utf8_sort, "utf8_join": cfg_utf8_join,
-         "topk": cfg_topk, "semi": cfg_semi, "tsmatch": cfg_tsmatch}[name](ctx, args.scale)
+         "topk": cfg_topk, "semi": cfg_semi, "tsmatch": cfg_tsmatch, "temporal": cfg_temporal}[name](ctx, args.scale)
         ctx.sync()
         abi.check(ctx.lib.qeh_pool_trim(ctx.h))
     ctx.close()
