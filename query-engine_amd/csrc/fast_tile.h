@@ -1,6 +1,7 @@
-// Fast-path column tiles shared by the fused join-aggregate (k_aggregate.hip) and the fused
-// filter + exchange pass (k_partition.hip): non-null 8-byte columns read as 16-B pairs, every load of a
-// tile issued before the term predicate is evaluated.
+// Fast-path column tiles shared by the fused join-aggregate (k_agg_probe.hip, k_aggregate.hip), the
+// single-key GROUP BY and the fused filter + exchange pass (k_partition.hip):
+// non-null 8-byte columns read as 16-B pairs, every load of a tile issued before the term predicate
+// is evaluated.
 #pragma once
 #include "agg.h"
 #include "device_common.h"

@@ -13,54 +13,22 @@
 // workgroup with global atomics) or directly with global atomics when the
 // states do not fit the LDS budget.  A finalize pass compacts non-empty
 // groups and converts states to the reference's result types.
+//
+// This unit holds the general path, the LDS-slice pipeline with its prelaunch, the distributed forms
+// and the top-level qeh_join_filter_aggregate.  The fast and bucket-range probes (k_agg_probe.hip),
+// the slice pipeline's materialising join (k_slice_join.hip) and the fused pipeline (k_agg_fused.hip)
+// are units of their own and reach this one's kernels through the launchers it exports (aggregate.h).
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
-#include <string>
 #include <memory>
+#include <optional>
+#include <string>
 #include <type_traits>
 
-#include "agg.h"
-#include "expr_device.h"
-#include "fast_tile.h"
-#include "ops.h"
+#include "aggregate.h"
 
 namespace qeh {
-
-constexpr int kAggR = 4;                           // rows per lane
-constexpr int kAggTile = kBlock * kAggR;           // rows per workgroup iteration
-constexpr size_t kLdsStateBudget = 48 * 1024;      // bytes of LDS state per workgroup
-constexpr int kFastTile = kBlock * kFastR;         // 2048 rows per fast-path workgroup iteration
-
-enum GidMode { GM_ZERO = 0, GM_JOIN = 1, GM_GROUP = 2, GM_LDSHASH = 3 };
-enum PredMode { PM_NONE = 0, PM_TERMS = 1, PM_PROG = 2 };
-
-constexpr int64_t kEmptyKey = INT64_MIN;
-struct GTable {                  // GM_LDSHASH: HBM table of group keys (EMPTY = INT64_MIN)
-    int64_t *keys;
-    uint64_t mask;               // capacity - 1; states index gcap = NULL group, gcap+1 = key INT64_MIN
-    uint32_t *overflow;
-};
-
-struct GidSource {
-    HashTable jt;            // GM_JOIN
-    int32_t key_col;         // GM_JOIN: probe key column in the ColSet
-    int32_t _pad;
-    KeyCols gk;              // GM_GROUP: key columns (absolute ColRefs)
-    const uint32_t *gslots;  // GM_GROUP
-    uint64_t gmask;
-    const uint64_t *gdense;
-    GTable gt;               // GM_LDSHASH
-    int32_t lcap;            // GM_LDSHASH: LDS slots per workgroup
-    int32_t _pad2;
-};
-
-// Global states are kept in specs.shards copies ([shard][slot][G]); workgroup b
-// merges into copy b % shards, so thousands of workgroups do not all hit the
-// same few KB with atomics.  k_states_reduce folds the copies into copy 0.
-__device__ __forceinline__ uint64_t *shard_states(uint64_t *all, const AggSpecs &specs, int64_t G) {
-    return all + (uint64_t)(blockIdx.x % (unsigned)specs.shards) * (uint64_t)specs.n_slots * (uint64_t)G;
-}
 
 template <int GM, int PM, bool LDS>
 __global__ __launch_bounds__(kBlock) void k_agg_rows(ColSet cols, int64_t n, PredTerms terms, DevProgram prog,
@@ -151,370 +119,6 @@ __global__ __launch_bounds__(kBlock) void k_agg_rows(ColSet cols, int64_t n, Pre
     }
 }
 
-// ---- fast fused probe: no-null 8-byte columns, unique join table (any layout) ----------
-// Each lane owns 8 rows as four 16-byte pairs (every load instruction of a
-// wave reads 1 KiB contiguous); all column loads of a tile are issued before
-// the predicate is evaluated, all table probes before any LDS update, so a
-// wave keeps 4 * (1 + terms + agg columns) HBM loads and 8 probes in flight.
-__device__ __forceinline__ bool probe_unique(const HashTable &t, int64_t key, uint32_t &gid) {
-    if (key < t.kmin || key > t.kmax) return false;
-    if (t.kind == TK_DIRECT) {
-        const uint64_t i = (uint64_t)key - (uint64_t)t.kmin;
-        uint32_t e = t.payload16 ? (uint32_t)t.payload16[i] : t.payload[i];
-        gid = e - 1u;
-        return e != 0;
-    }
-    if (t.kind == TK_BUCKET) {
-        const int S = bucket_slots(t.pbits);
-        uint64_t b = bucket_home(t, (uint64_t)key);
-        for (uint64_t step = 0; step < t.nbkt; ++step) {
-            uint64_t w[8];
-            bucket_load(t, b, w);
-            const uint32_t cnt = (uint32_t)(w[7] >> 32);
-            // every slot compared with constant register indices (a runtime slot index into w
-            // costs a chain of selects per access), the payload picked the same way
-            uint32_t hit = 0;
-#pragma unroll
-            for (int s = 0; s < 6; ++s) hit |= (s < S && s < (int)cnt && (int64_t)w[s] == key) ? 1u << s : 0u;
-            if (hit) {
-                const int s0 = __builtin_ctz(hit);
-                uint32_t pl = 0;
-#pragma unroll
-                for (int s = 0; s < 6; ++s)
-                    if (s == s0) pl = bucket_payload(w, s, t.pbits);
-                gid = pl - 1u;
-                return true;
-            }
-            if (cnt <= (uint32_t)S) return false;
-            b = b + 1 == t.nbkt ? 0 : b + 1;
-        }
-        return false;
-    }
-    uint64_t h = hash64((uint64_t)key) & t.mask;
-    if (t.kind == TK_WIDE) {
-        for (uint64_t i = 0; i <= t.mask; ++i) {
-            const v2u64 e = wide_slot(t, h);
-            if (e[1] == 0) return false;
-            if ((int64_t)e[0] == key) {
-                gid = (uint32_t)(e[1] - 1ull);
-                return true;
-            }
-            h = (h + 1) & t.mask;
-        }
-        return false;
-    }
-    const uint64_t want = (uint64_t)key - (uint64_t)t.kmin + 1ull;
-    for (uint64_t i = 0; i <= t.mask; ++i) {
-        uint64_t e = t.slots[h];
-        if (e == 0) return false;
-        if ((e >> t.pbits) == want) {
-            gid = (uint32_t)(e & ((1ull << t.pbits) - 1ull));
-            return true;
-        }
-        h = (h + 1) & t.mask;
-    }
-    return false;
-}
-
-// Apply one tile's rows (mask m, LDS state slot per row) to LDS states laid
-// out [value slot][stride] with row counts in slot 0.  Aggregate kinds are
-// uniform, so the switch sits outside the row loop and each aggregate's LDS
-// atomics for the tile's rows issue back to back.
-template <int NTERMS, int NACOL, bool NT>
-__device__ __forceinline__ void lds_apply_rows(uint64_t *lds, int64_t stride, const AggSpecs &specs, const FastIn &in,
-                                               const FastTile<NTERMS, NACOL, NT> &ft, uint32_t m, const int *slot) {
-#pragma unroll
-    for (int r = 0; r < kFastR; ++r)
-        if ((m >> r) & 1) atomicAdd((unsigned long long *)&lds[slot[r]], 1ull);
-    for (int a = 0; a < specs.n; ++a) {
-        const AggSpec sp = specs.a[a];
-        uint64_t *st = lds + (int64_t)sp.val_slot * stride;
-        const int cs = in.agg_colslot[a];
-        switch (sp.kind) {
-            case AK_SUM_F:
-#pragma unroll
-                for (int r = 0; r < kFastR; ++r)
-                    if ((m >> r) & 1) atomicAdd((double *)&st[slot[r]], as_f64(ft.a(cs, r)));
-                break;
-            case AK_SUM_I:
-#pragma unroll
-                for (int r = 0; r < kFastR; ++r)
-                    if ((m >> r) & 1) atomicAdd((unsigned long long *)&st[slot[r]], (unsigned long long)ft.a(cs, r));
-                break;
-            case AK_MIN:
-            case AK_MAX:
-#pragma unroll
-                for (int r = 0; r < kFastR; ++r)
-                    if ((m >> r) & 1) agg_apply<true>(sp.kind, &st[slot[r]], agg_input(sp.kind, sp.in_type, ft.a(cs, r)));
-                break;
-            default: break;  // COUNT of a no-null column = the row count
-        }
-    }
-}
-
-template <int NTERMS, int NACOL, bool NT>
-__global__ __launch_bounds__(kBlock) void k_join_agg_fast(FastIn in, PredTerms terms, AggSpecs specs, HashTable t,
-                                                          int64_t G, int64_t n_tiles, uint64_t *__restrict__ gstates_all) {
-    uint64_t *__restrict__ gstates = shard_states(gstates_all, specs, G);
-    extern __shared__ __attribute__((aligned(16))) uint64_t lds[];
-    {
-        const int64_t words = (int64_t)specs.n_slots * G;
-        for (int64_t i = threadIdx.x; i < words; i += blockDim.x) lds[i] = 0;
-        __syncthreads();
-        for (int a = 0; a < specs.n; ++a) {
-            const AggSpec sp = specs.a[a];
-            if (sp.kind == AK_MIN || sp.kind == AK_MAX)
-                for (int64_t g = threadIdx.x; g < G; g += blockDim.x) lds[(int64_t)sp.val_slot * G + g] = (uint64_t)agg_init_value(sp.kind);
-        }
-        __syncthreads();
-    }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-        const int64_t base = tile * kFastTile + (int64_t)wave * (64 * kFastR) + 2 * lane;
-        FastTile<NTERMS, NACOL, NT> ft;
-        ft.load(in, terms, base);
-        const uint32_t sel = ft.sel;
-        uint32_t gid[kFastR];
-        int slot[kFastR];
-        uint32_t hit = 0;
-#pragma unroll
-        for (int r = 0; r < kFastR; ++r) {
-            gid[r] = 0;
-            if ((sel >> r) & 1)
-                if (probe_unique(t, ft.k(r), gid[r])) hit |= 1u << r;
-            slot[r] = (int)gid[r];
-        }
-        lds_apply_rows(lds, G, specs, in, ft, hit, slot);
-    }
-    __syncthreads();
-    for (int64_t g = threadIdx.x; g < G; g += blockDim.x) {
-        uint64_t rows = lds[g];
-        if (!rows) continue;
-        atomicAdd((unsigned long long *)&gstates[g], (unsigned long long)rows);
-        for (int a = 0; a < specs.n; ++a) {
-            const AggSpec sp = specs.a[a];
-            if (sp.kind != AK_COUNT)
-                agg_merge_global(sp.kind, &gstates[(int64_t)sp.val_slot * G + g], lds[(int64_t)sp.val_slot * G + g]);
-        }
-    }
-}
-
-// ---- bucket-range partitioned probe (BUCKET tables: sparse 64-bit keys; opt-in, see try_bucket_parts) --
-// A BUCKET table of 1e7 sparse keys is 178 MB: the single fused pass (k_join_agg_fast) reads one 64-B
-// bucket line per selected probe row from the Infinity Cache.  Here the probe rows are first split by
-// the high bits of the key's hash -- the home bucket is monotone in the hash, so each of the 64
-// partitions owns a contiguous 1/64 of the table (2.8 MB at 1e7 keys) -- and each partition is then
-// probed by the workgroups of one XCD together, so its part of the table stays in that XCD's 4 MB L2.
-//   P1 k_bp_part: FastTile loads + predicate; the selected rows' (key, aggregate input) are staged in
-//      LDS by partition and appended to the workgroup's open 256-item chunk per partition (chunks from
-//      one global counter, tagged with their partition; runs of ~32 rows per partition per tile).
-//   P2 k_bp_probe: XCD x (blockIdx % 8) takes partitions x, x + 8, ...; its workgroups split each
-//      partition's chunk list (chunk_lists), probe the table (L2 hits) and aggregate in LDS states.
-// HBM bytes per probe row: 24 read (x, k, v) + 16 written and read back per selected row; the table
-// once per partition.  A key stored past its partition's last bucket (linear probing by buckets) is
-// still found: the probe reads the real table.
-constexpr int kBpBlock = 512;
-constexpr int kBpWaves = kBpBlock / 64;
-constexpr int kBpTile = kBpBlock * kFastR;  // 4096 probe rows per P1 iteration
-constexpr int kBpPBits = 6;
-constexpr int kBpP = 1 << kBpPBits;         // partitions
-constexpr int kBpChunk = 256;
-
-// LDS-only workgroup barrier: the next tile's loads stay in flight across it
-__device__ __forceinline__ void bp_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
-template <int NTERMS, int NACOL, bool NT>
-__global__ __launch_bounds__(kBpBlock) void k_bp_part(FastIn in, PredTerms terms, int64_t n, int acs,
-                                                      uint64_t *__restrict__ okey, uint64_t *__restrict__ oval,
-                                                      uint16_t *__restrict__ tag, uint16_t *__restrict__ ccnt,
-                                                      uint32_t *__restrict__ nchunk) {
-    __shared__ uint32_t pc[kBpP], tstart[kBpP], fillp[kBpP], curc[kBpP], cbase[kBpP];
-    __shared__ uint64_t skey[kBpTile];
-    __shared__ uint64_t sval[NACOL > 0 ? kBpTile : 1];
-    __shared__ uint32_t sdst[kBpTile];
-    __shared__ uint32_t tot_s;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    if (tid < kBpP) pc[tid] = 0, fillp[tid] = kBpChunk, curc[tid] = 0;  // fill 256: no open chunk
-    __syncthreads();
-    const int64_t n_tiles = (n + kBpTile - 1) / kBpTile;
-    const int64_t woff = (int64_t)wave * (64 * kFastR) + 2 * lane;
-    // the next tile's loads are issued before this tile's LDS phases (full tiles; the ragged last tile
-    // is loaded on its own)
-    FastTile<NTERMS, NACOL, NT> nx;
-    if ((int64_t)blockIdx.x < n_tiles && ((int64_t)blockIdx.x + 1) * kBpTile <= n) nx.issue(in, (int64_t)blockIdx.x * kBpTile + woff);
-    for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-        const int64_t base = tile * kBpTile + woff;
-        FastTile<NTERMS, NACOL, NT> ft;
-        if ((tile + 1) * kBpTile <= n) {
-            ft = nx;
-            ft.eval(in, terms);
-            const int64_t t2 = tile + gridDim.x;
-            if (t2 < n_tiles && (t2 + 1) * kBpTile <= n) nx.issue(in, t2 * kBpTile + woff);
-        } else {
-            ft.issue_tail(in, base, n);
-            ft.eval(in, terms);
-            ft.sel &= FastTile<NTERMS, NACOL, NT>::tail_mask(base, n);
-        }
-        uint32_t part[kFastR], rk[kFastR];
-#pragma unroll
-        for (int r = 0; r < kFastR; ++r) {
-            part[r] = (uint32_t)(hash64((uint64_t)ft.k(r)) >> (64 - kBpPBits));
-            rk[r] = ((ft.sel >> r) & 1u) ? atomicAdd(&pc[part[r]], 1u) : 0u;
-        }
-        bp_barrier();
-        if (tid < kBpP) {  // wave 0: the tile's starts, and the chunks each partition opens
-            const uint32_t c = pc[tid];
-            const uint32_t incl = wave_incl_scan(c);
-            tstart[tid] = incl - c;
-            if (tid == kBpP - 1) tot_s = incl;
-            const uint32_t room = kBpChunk - fillp[tid];
-            const uint32_t spill = c > room ? c - room : 0u;
-            const uint32_t nnew = (spill + kBpChunk - 1) / kBpChunk;
-            uint32_t b = 0;
-            if (nnew) {
-                b = atomicAdd(nchunk, nnew);
-                for (uint32_t i = 0; i < nnew; ++i) tag[b + i] = (uint16_t)tid, ccnt[b + i] = (uint16_t)kBpChunk;
-            }
-            cbase[tid] = b;
-        }
-        bp_barrier();
-#pragma unroll
-        for (int r = 0; r < kFastR; ++r) {
-            if (!((ft.sel >> r) & 1u)) continue;
-            const uint32_t p = part[r], f = fillp[p], room = kBpChunk - f;
-            uint32_t dst;
-            if (rk[r] < room) {
-                dst = curc[p] * kBpChunk + f + rk[r];
-            } else {
-                const uint32_t q = rk[r] - room;
-                dst = (cbase[p] + q / kBpChunk) * kBpChunk + q % kBpChunk;
-            }
-            const uint32_t st = tstart[p] + rk[r];
-            skey[st] = (uint64_t)ft.k(r);
-            if (NACOL > 0) sval[st] = (uint64_t)ft.a(acs, r);
-            sdst[st] = dst;
-        }
-        bp_barrier();
-        const uint32_t tot = tot_s;
-        for (uint32_t i = tid; i < tot; i += kBpBlock) {
-            const uint32_t d = sdst[i];
-            okey[d] = skey[i];
-            if (NACOL > 0) oval[d] = sval[i];
-        }
-        if (tid < kBpP) {
-            const uint32_t c = pc[tid], f = fillp[tid], room = kBpChunk - f;
-            if (c <= room) {
-                fillp[tid] = f + c;
-            } else {
-                const uint32_t q = c - room;
-                curc[tid] = cbase[tid] + (q - 1) / kBpChunk;
-                fillp[tid] = (q - 1) % kBpChunk + 1;
-            }
-            pc[tid] = 0;
-        }
-        bp_barrier();
-    }
-    if (tid < kBpP && fillp[tid] < kBpChunk) ccnt[curc[tid]] = (uint16_t)fillp[tid];
-}
-
-template <int NACOL>
-__global__ __launch_bounds__(kBpBlock) void k_bp_probe(AggSpecs specs, FastIn in, HashTable t, int64_t G,
-                                                       const uint32_t *__restrict__ sbase, const uint32_t *__restrict__ list,
-                                                       const uint64_t *__restrict__ ikey, const uint64_t *__restrict__ ival,
-                                                       uint64_t *__restrict__ gstates_all) {
-    uint64_t *__restrict__ gstates = shard_states(gstates_all, specs, G);
-    extern __shared__ __attribute__((aligned(16))) uint64_t lds[];
-    {
-        const int64_t words = (int64_t)specs.n_slots * G;
-        for (int64_t i = threadIdx.x; i < words; i += blockDim.x) lds[i] = 0;
-        __syncthreads();
-        for (int a = 0; a < specs.n; ++a) {
-            const AggSpec sp = specs.a[a];
-            if (sp.kind == AK_MIN || sp.kind == AK_MAX)
-                for (int64_t g = threadIdx.x; g < G; g += blockDim.x) lds[(int64_t)sp.val_slot * G + g] = (uint64_t)agg_init_value(sp.kind);
-        }
-        __syncthreads();
-    }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int x = blockIdx.x & 7;
-    const uint32_t wi = blockIdx.x >> 3, nwg = gridDim.x >> 3;
-    constexpr int U = 2;  // chunks per wave in flight (8 probes per lane)
-    for (int p = x; p < kBpP; p += 8) {
-        const uint32_t lo = sbase[p], hi = sbase[p + 1];
-        const uint32_t stride = nwg * kBpWaves * U;
-        uint32_t ent[U];  // this iteration's list entries (the next ones are read while it probes)
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const uint32_t e = lo + (wi * kBpWaves + wave) * U + u;
-            ent[u] = e < hi ? list[e] : 0xFFFFFFFFu;
-        }
-        for (uint32_t e0 = lo + (wi * kBpWaves + wave) * U; e0 < hi; e0 += stride) {
-            int64_t key[U][4], val[U][4];
-            uint32_t cn[U];
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                cn[u] = ent[u] == 0xFFFFFFFFu ? 0u : (ent[u] >> 24) + 1u;
-                const uint64_t at = (uint64_t)(ent[u] & 0xFFFFFFu) * kBpChunk + lane * 4;
-                if (cn[u]) {
-                    const v2i64 k0 = __builtin_nontemporal_load((const v2i64 *)(ikey + at));
-                    const v2i64 k1 = __builtin_nontemporal_load((const v2i64 *)(ikey + at + 2));
-                    key[u][0] = k0[0], key[u][1] = k0[1], key[u][2] = k1[0], key[u][3] = k1[1];
-                    if (NACOL > 0) {
-                        const v2i64 v0 = __builtin_nontemporal_load((const v2i64 *)(ival + at));
-                        const v2i64 v1 = __builtin_nontemporal_load((const v2i64 *)(ival + at + 2));
-                        val[u][0] = v0[0], val[u][1] = v0[1], val[u][2] = v1[0], val[u][3] = v1[1];
-                    }
-                }
-            }
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const uint32_t e = e0 + stride + u;
-                ent[u] = e < hi ? list[e] : 0xFFFFFFFFu;
-            }
-            uint32_t gid[U][4];
-            uint32_t hit = 0;
-#pragma unroll
-            for (int u = 0; u < U; ++u)
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    gid[u][q] = 0;
-                    if ((uint32_t)(lane * 4 + q) < cn[u] && probe_unique(t, key[u][q], gid[u][q])) hit |= 1u << (u * 4 + q);
-                }
-#pragma unroll
-            for (int u = 0; u < U; ++u)
-#pragma unroll
-                for (int q = 0; q < 4; ++q)
-                    if ((hit >> (u * 4 + q)) & 1u) atomicAdd((unsigned long long *)&lds[gid[u][q]], 1ull);
-            for (int a = 0; a < specs.n; ++a) {
-                const AggSpec sp = specs.a[a];
-                if (sp.kind == AK_COUNT || in.agg_colslot[a] < 0) continue;
-                uint64_t *st = lds + (int64_t)sp.val_slot * G;
-#pragma unroll
-                for (int u = 0; u < U; ++u)
-#pragma unroll
-                    for (int q = 0; q < 4; ++q)
-                        if ((hit >> (u * 4 + q)) & 1u) {
-                            const int64_t v = NACOL > 0 ? val[u][q] : 0;
-                            if (sp.kind == AK_SUM_F) atomicAdd((double *)&st[gid[u][q]], as_f64(v));
-                            else if (sp.kind == AK_SUM_I) atomicAdd((unsigned long long *)&st[gid[u][q]], (unsigned long long)v);
-                            else agg_apply<true>(sp.kind, &st[gid[u][q]], agg_input(sp.kind, sp.in_type, v));
-                        }
-            }
-        }
-    }
-    __syncthreads();
-    for (int64_t g = threadIdx.x; g < G; g += blockDim.x) {
-        uint64_t rows = lds[g];
-        if (!rows) continue;
-        atomicAdd((unsigned long long *)&gstates[g], (unsigned long long)rows);
-        for (int a = 0; a < specs.n; ++a) {
-            const AggSpec sp = specs.a[a];
-            if (sp.kind != AK_COUNT)
-                agg_merge_global(sp.kind, &gstates[(int64_t)sp.val_slot * G + g], lds[(int64_t)sp.val_slot * G + g]);
-        }
-    }
-}
-
 // ---- LDS-slice partitioned probe (direct u16 tables larger than L2) ----------------
 // A single fused pass pays one L2 miss (a 64-B Infinity-Cache request) per
 // probe once the table outgrows an XCD's 4 MiB L2; at the BASELINE shape
@@ -530,100 +134,11 @@ __global__ __launch_bounds__(kBpBlock) void k_bp_probe(AggSpecs specs, FastIn in
 //     that slice's regions with LDS lookups and LDS aggregate states.
 // HBM bytes per selected row: 2 + 8*NACOL written and read back; lookups
 // cost LDS cycles only.
-constexpr int kSliceBits = 16;
-constexpr int kSliceKeys = 1 << kSliceBits;
-constexpr int kSliceMaxF = 160;                  // slices: key range <= 160 * 65536
-constexpr int kSliceBlock = 1024;                // one workgroup per CU in both phases
-constexpr int kSliceTile = kSliceBlock * kFastR;  // 8192 probe rows per phase-A iteration
-constexpr int kSliceChunk = 32;                  // items per flushed chunk
-constexpr int kMaxSliceGrid = 512;               // phase-A workgroups / build regions (items form) phase B walks
-constexpr int kSliceStateWords = 3584;           // phase-B LDS aggregate states (n_slots * G)
-// Group-range slices (G too large for LDS states): phase A looks the group id up and partitions
-// by gid >> kGidSliceBits; phase B aggregates one range of 2^kGidSliceBits groups in LDS.
-constexpr int kGidSliceBits = 12;
-constexpr int kGidStateWords = 16384;            // n_slots * 2^kGidSliceBits <= this (128 KB)
 
 // Workgroup barrier ordering LDS only: the next tile's global loads stay in
 // flight across it (__syncthreads also drains vmcnt).
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
-struct SliceRegions {
-    uint16_t *key;        // [grid][F][cap] key - kmin - slice * 2^16
-    int64_t *val;         // [grid][F][cap] aggregate input (NACOL >= 1)
-    int64_t *val2;        // [grid][F][cap] second aggregate input (NACOL == 2)
-    uint32_t *count;      // [grid][F]
-    uint32_t *overflow;   // set when a region fills up (skewed probe keys)
-    uint64_t cap;         // items per region, multiple of kSliceChunk
-    int32_t F;            // slices
-    // exact layout (materialising join): region (workgroup r, slice b) starts at
-    // rbase[b * grid + r] (slice-major, no gaps) instead of (r * F + b) * cap
-    const uint64_t *rbase;
-    // partitioned layout (the shuffle join's items form, pw > 0 ranks). Phase A: region (w, b) is number
-    // part_region(b, w), slice-major with the slices of one destination rank (b % pw) together -- rank q's
-    // regions are one contiguous block. Phase B: the packed regions received from pw ranks, local slice
-    // j (global slice j * pw + prank) region (q, w) numbered (q * S + j) * pgrid + w, at rbase[number].
-    int32_t pw;
-    int32_t prank;
-    int32_t pgrid;
-    // phase B of the partitioned layout: this rank's own regions (source prank) read in place from phase
-    // A's layout (region number * ocap) instead of from the packed receive buffers
-    const uint16_t *okey;
-    const int64_t *oval;
-    uint64_t ocap;
-};
-// the partitioned layout's slices per rank and a region's number (phase A, pw > 0)
-__host__ __device__ __forceinline__ int part_slices(int F, int pw) { return (F + pw - 1) / pw; }
-__host__ __device__ __forceinline__ uint64_t part_region(int b, int w, int F, int pw, int grid) {
-    return ((uint64_t)(b % pw) * part_slices(F, pw) + (uint64_t)(b / pw)) * grid + w;
-}
-
-
-// Phase A's shape when it is planned on the device (the prelaunch ahead of the build reads the build
-// key's range from device memory instead of waiting for the host: no host round trip between the
-// min/max kernels and phase A).  plan_slices is the one rule, evaluated on the device by
-// k_slice_plan and on the host to adopt the result; regions are allocated for the worst case and
-// the plan's cap divides them among grid x F regions.
-struct SlicePlan {
-    int64_t kmin;
-    uint64_t range;
-    uint64_t cap;
-    int32_t F;
-    int32_t ok;
-    int64_t src[6];  // the build ranges it was planned from: key min, max, count, group key min, max, count
-};
-struct SlicePlanIn {
-    uint64_t min_bytes;    // smallest table (bytes) worth the two-phase pipeline
-    uint64_t alloc_items;  // items allocated for all regions together
-    int32_t grid;
-    int32_t n_slots;
-    int32_t sparse_ok;     // direct_table_ok's sparse rule enabled
-    int32_t chunk;         // items per flushed chunk (regions are whole chunks); 0 = kSliceChunk
-    int32_t world;         // > 1: the partitioned layout's regions (F rounded up to a multiple of world)
-};
-__host__ __device__ inline SlicePlan plan_slices(const SlicePlanIn &pi, int64_t kmn, int64_t kmx, int64_t kcnt, int64_t gmn,
-                                                 int64_t gmx, int64_t gcnt) {
-    SlicePlan p{};
-    p.src[0] = kmn, p.src[1] = kmx, p.src[2] = kcnt, p.src[3] = gmn, p.src[4] = gmx, p.src[5] = gcnt;
-    if (kcnt <= 0) return p;
-    // the group count is at most the group key's range (+ the NULL group)
-    const uint64_t gr = gcnt ? (uint64_t)gmx - (uint64_t)gmn + 1ull : 0;
-    const int64_t g_bound = (gr == 0 || gr > (1ull << 20)) ? -1 : (int64_t)gr + 1;
-    if (g_bound <= 0 || g_bound >= 0xFFFF || (int64_t)pi.n_slots * g_bound > kSliceStateWords) return p;
-    const uint64_t range = (uint64_t)kmx - (uint64_t)kmn + 1ull;
-    // the DIRECT rule of build_join_table, and the slice path's own limits
-    if (!direct_table_ok_with(range, (uint64_t)kcnt, (uint64_t)g_bound, pi.sparse_ok != 0)) return p;
-    if (range * 2 < pi.min_bytes) return p;
-    const uint64_t F = (range + kSliceKeys - 1) >> kSliceBits;
-    if (F == 0 || F > (uint64_t)kSliceMaxF) return p;
-    p.kmin = kmn;
-    p.range = range;
-    p.F = (int32_t)F;
-    const uint64_t ch = pi.chunk > 0 ? (uint64_t)pi.chunk : (uint64_t)kSliceChunk;
-    const uint64_t Fr = pi.world > 1 ? (F + pi.world - 1) / pi.world * pi.world : F;  // regions' slices
-    p.cap = pi.alloc_items / ((uint64_t)pi.grid * Fr) / ch * ch;
-    p.ok = p.cap >= ch;
-    return p;
-}
 // mm[0] = build key, mm[1] = group key ranges
 __global__ void k_slice_plan(const MinMax *__restrict__ mm, SlicePlanIn pi, SlicePlan *out) {
     if (threadIdx.x == 0 && blockIdx.x == 0)
@@ -647,47 +162,6 @@ __global__ void k_slice_plan_stats(const int64_t *__restrict__ M, int world, int
     if (bitmap || kmn > kmx || gmn > gmx) p.ok = 0;
     *out = p;
 }
-
-// The fused pipeline's plan (qeh_join_filter_aggregate with one bounded integer group key): the slice
-// shape of the build key's range plus the group key's range -- the join table's entries are group
-// slots (g - gmin + 1) instead of dense group ids, so the build needs no group table first.
-struct FusedPlan {
-    SlicePlan sp;      // sp.ok: every condition of the fused pipeline holds
-    int64_t gmin;      // group slot s <-> group key gmin + s
-    int64_t ngroups;   // gmax - gmin + 1
-    uint64_t dcap;     // build rows per (phase-A workgroup, slice) region, a multiple of 4
-};
-// Phase A's prologue in the fused pipeline: the build rows grouped by slice into per-(workgroup,
-// slice) regions (items = key offset << 16 | group slot + 1), and the output group keys.
-struct FusedPro {
-    const int64_t *dk;     // build key (Int64, no NULLs)
-    ColRef dg;             // group key (Int64 / Int32, no NULLs)
-    int64_t nd;
-    uint32_t *ditems;      // [grid][F][dcap]
-    uint32_t *dcount;      // [grid][F]
-    uint32_t *status;      // [1]: a region overflowed (probe or build rows)
-    void *gkeys;           // output group keys: gmin + i for i < G (Int32 when as32)
-    uint32_t *rep;         // i (the finalize's representative rows)
-    int64_t G;
-    int32_t as32;
-    const FusedPlan *plan;
-};
-// Phase B's view of the build rows (DIM): slice b's rows are items[(r * F + b) * dcap ..] for every
-// phase-A workgroup r, count[r * F + b] of them.
-struct DimSlices {
-    const uint32_t *items;
-    const uint32_t *count;
-    uint32_t *dup;     // set when two build rows share a key
-    const FusedPlan *plan;
-    // the items form of the distributed broadcast join: the build rows come grouped by slice from the
-    // ranks instead of from phase A's prologue -- nreg > 0 regions (every rank's build spans), region r's
-    // items at items + r * rstride, with o = offs + r * 2 * (kSliceMaxF + 1): slice b's o[S + 1 + b] items
-    // at o[b] (a multiple of 4)
-    int32_t nreg;
-    int32_t _pad;
-    uint64_t rstride;
-    const uint32_t *offs;
-};
 
 // One whole chunk of phase A's flush, planned by the slice's owner thread while the tile is staged:
 // item x of the chunk (x < CH) comes from the carried items (c_key/c_v[coff + x]) when x < clim, else
@@ -714,23 +188,11 @@ struct __attribute__((aligned(16))) SliceChunk {
 // EARLY (the fused pipeline) may take its own tile and chunk (QEH_EARLY_PAIRS / QEH_EARLY_CHUNK at
 // build time): 64-item chunks (128 B of keys + 512 B of values, whole lines) with 4096-row tiles keep
 // the carries and the staging in one CU's LDS.
-#ifndef QEH_EARLY_PAIRS
-#define QEH_EARLY_PAIRS 2
-#endif
 // 1: tile t-1's flush after tile t's rows are ranked (and, EARLY, tile t+1's loads issued); 0: at the
 // top of the iteration, before tile t's loads are waited for (the round-4 order)
 #ifndef QEH_SLICE_FLUSH_LATE
 #define QEH_SLICE_FLUSH_LATE 1
 #endif
-#ifndef QEH_EARLY_CHUNK
-#define QEH_EARLY_CHUNK 64
-#endif
-template <int NACOL, bool EARLY = false, int NTH = kSliceBlock>
-struct SliceShape {
-    static constexpr int P = NACOL > 1 ? 2 : (EARLY ? QEH_EARLY_PAIRS : kFastPairs);
-    static constexpr int CH = NACOL > 1 ? 16 : (EARLY ? QEH_EARLY_CHUNK : kSliceChunk);
-    static constexpr int TILE = NTH * 2 * P;
-};
 
 // Phase A's prologue in the fused pipeline (before the first tile's loads): the output group keys,
 // then this workgroup's share of the build rows, each into its slice's region (LDS atomics on dcnt
@@ -1541,299 +1003,6 @@ __global__ __launch_bounds__(kSliceBlock) void k_slice_keyagg(SliceRegions rg, i
     if (C16 && ovf) *rg.overflow = 1u;
 }
 
-// ---- fused pipeline: the plan -----------------------------------------------------------------
-// The build rows (key, group key) take the probe rows' route: phase A's prologue groups them by slice
-// (4-B items), and phase B builds each slice's entries in LDS from them instead of loading a join table
-// from HBM.  No table is written, there are no scattered 2-B stores (the XCD-split insert read every
-// key 8 times, 1.2 GB per query), and nothing of the build runs beside phase A.
-// mm[0] = build key, mm[1] = group key ranges; nd = build rows (no NULLs allowed); dim_items = the
-// build-row region buffer's size in items; st = the status words (zeroed here, [5] = the verdict).
-// One launch ahead of phase A: workgroup 0 reduces the build key / group key partial min / max
-// (part[c * nb + w], c = 0 key, 1 group key) and writes the plan and the zeroed status words; every
-// workgroup initialises its share of the aggregate states.
-__global__ __launch_bounds__(1024) void k_fused_plan(const MinMax *__restrict__ part, int nb, SlicePlanIn pi, int64_t g_cap,
-                                                     int64_t nd, uint64_t dim_items, FusedPlan *out, uint32_t *__restrict__ st,
-                                                     uint64_t *__restrict__ states, int64_t G, AggSpecs specs) {
-    const int64_t words = (int64_t)specs.shards * specs.n_slots * G;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < words; i += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t slot = (i / G) % specs.n_slots;
-        uint64_t v = 0;
-        for (int a = 0; a < specs.n; ++a)
-            if (specs.a[a].val_slot == slot) v = (uint64_t)agg_init_value(specs.a[a].kind);
-        states[i] = v;
-    }
-    if (blockIdx.x != 0) return;
-    __shared__ MinMax sm[2][16];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (int c = 0; c < 2; ++c) {
-        int64_t mn = INT64_MAX, mx = INT64_MIN;
-        uint64_t cnt = 0;
-        uint32_t bad = 0;
-        for (int i = threadIdx.x; i < nb; i += blockDim.x) {
-            const MinMax q = part[(int64_t)c * nb + i];
-            mn = q.mn < mn ? q.mn : mn;
-            mx = q.mx > mx ? q.mx : mx;
-            cnt += q.cnt;
-            bad |= q.bad;
-        }
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) {
-            const int64_t a = __shfl_xor(mn, d, 64), b2 = __shfl_xor(mx, d, 64);
-            const uint64_t cc = __shfl_xor(cnt, d, 64);
-            const uint32_t bb = __shfl_xor(bad, d, 64);
-            mn = a < mn ? a : mn;
-            mx = b2 > mx ? b2 : mx;
-            cnt += cc;
-            bad |= bb;
-        }
-        if (lane == 0) sm[c][wave] = MinMax{mn, mx, cnt, bad};
-    }
-    __syncthreads();
-    if (threadIdx.x != 0) return;
-    MinMax mm[2];
-    for (int c = 0; c < 2; ++c) {
-        mm[c] = sm[c][0];
-        for (int w = 1; w < (int)(blockDim.x >> 6); ++w) {
-            const MinMax q = sm[c][w];
-            mm[c].mn = q.mn < mm[c].mn ? q.mn : mm[c].mn;
-            mm[c].mx = q.mx > mm[c].mx ? q.mx : mm[c].mx;
-            mm[c].cnt += q.cnt;
-            mm[c].bad |= q.bad;
-        }
-    }
-    FusedPlan p{};
-    p.sp = plan_slices(pi, mm[0].mn, mm[0].mx, (int64_t)mm[0].cnt, mm[1].mn, mm[1].mx, (int64_t)mm[1].cnt);
-    const bool full = (int64_t)mm[0].cnt == nd && (int64_t)mm[1].cnt == nd && !mm[0].bad && !mm[1].bad;
-    p.gmin = mm[1].mn;
-    p.ngroups = full ? (int64_t)((uint64_t)mm[1].mx - (uint64_t)mm[1].mn + 1ull) : 0;
-    p.dcap = p.sp.F > 0 ? dim_items / ((uint64_t)pi.grid * p.sp.F) / 4 * 4 : 0;
-    p.sp.ok = p.sp.ok && full && p.ngroups >= 1 && p.ngroups <= g_cap && p.ngroups < 0xFFFF && p.dcap >= 4;
-    *out = p;
-    for (int i = 0; i < 8; ++i) st[i] = 0u;
-    st[5] = p.sp.ok ? 1u : 0u;
-}
-
-// ---- LDS-slice materialising INNER join (BASELINE config 3) -----------------------------
-// Same phase A as the aggregate (k_slice_partition: items = 16-bit key offset +
-// the probe payload).  Phase B writes the joined rows: the build payload is
-// stored in the u16 table as (a - amin) + 1, so a slice in LDS answers both
-// "matches?" and "with which value?".  Rows leave in slice order (the join's
-// row order is not part of its contract); each wave reserves
-// its matches with one atomic per 512 items and writes them contiguously.
-// write the wave's matches of one 8-items-per-lane step at out[*base ...]
-// (j-major, lanes in order within j: contiguous stores), advancing *base
-__device__ __forceinline__ void emit_matches(const uint32_t *e, const int64_t *v, const bool *live, int64_t amin,
-                                             uint64_t *base, int64_t *__restrict__ out_v, int64_t *__restrict__ out_a) {
-    uint64_t b = *base;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const bool m = live[j] && e[j] != 0u;
-        const uint64_t mask = __ballot(m);
-        if (m) {
-            const uint64_t pos = b + mbcnt(mask);
-            out_v[pos] = v[j];
-            out_a[pos] = (int64_t)(e[j] - 1u) + amin;
-        }
-        b += popc64(mask);
-    }
-    *base = b;
-}
-
-__device__ __forceinline__ void load_slice(uint16_t *tslice, const HashTable &t, int b, int tid) {
-    const uint64_t k0 = (uint64_t)b << kSliceBits;
-    const uint64_t nk = t.range - k0 < (uint64_t)kSliceKeys ? t.range - k0 : (uint64_t)kSliceKeys;
-    for (int i = tid * 8; i < kSliceKeys; i += kSliceBlock * 8) {
-        v4u32 w = {0u, 0u, 0u, 0u};
-        if ((uint64_t)i + 8 <= nk) {
-            w = *(const v4u32 *)(t.payload16 + k0 + i);
-        } else {
-            for (int q = 0; q < 8; ++q)
-                if ((uint64_t)(i + q) < nk) w[q >> 1] |= (uint32_t)t.payload16[k0 + i + q] << ((q & 1) * 16);
-        }
-        *(v4u32 *)&tslice[i] = w;
-    }
-}
-
-// Phase B of the join in two passes, no atomics: EMIT = false counts each
-// region's matches (keys only) into counts[slot]; after an exclusive scan of
-// those (slot order), EMIT = true writes each region's matches from its base.
-template <bool EMIT>
-__global__ __launch_bounds__(kSliceBlock) void k_slice_join_b(SliceRegions rg, int nreg, HashTable t, int64_t amin,
-                                                              uint32_t *__restrict__ counts, const uint64_t *__restrict__ bases,
-                                                              int64_t *__restrict__ out_v, int64_t *__restrict__ out_a) {
-    __shared__ __attribute__((aligned(16))) uint16_t tslice[kSliceKeys];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    constexpr int W = kSliceBlock / 64;
-    const int F = rg.F;
-    const int64_t T = (int64_t)F * nreg;
-    const int64_t s0 = (int64_t)blockIdx.x * T / gridDim.x, s1 = (int64_t)(blockIdx.x + 1) * T / gridDim.x;
-    for (int64_t sb = s0; sb < s1;) {
-        const int b = (int)(sb / nreg);
-        const int64_t se = std::min<int64_t>(s1, (int64_t)(b + 1) * nreg);
-        __syncthreads();
-        load_slice(tslice, t, b, tid);
-        __syncthreads();
-        for (int64_t s = sb + wave; s < se; s += W) {
-            const uint64_t reg = (uint64_t)(s - (int64_t)b * nreg) * F + b;
-            const uint32_t n_r = rg.count[reg];
-            const uint64_t rb = rg.rbase ? rg.rbase[s] : reg * rg.cap;
-            const uint16_t *kp = rg.key + rb;
-            const int64_t *vp = rg.val + rb;
-            uint64_t base = EMIT ? bases[s] : 0;
-            uint32_t matches = 0;
-            for (uint32_t i0 = 0; i0 < n_r; i0 += 64 * 8) {
-                uint32_t e[8];
-                int64_t v[8];
-                bool live[8];
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    const uint32_t i = i0 + j * 64 + lane;
-                    live[j] = i < n_r;
-                    const uint32_t ii = live[j] ? i : 0u;
-                    e[j] = __builtin_nontemporal_load(kp + ii);
-                    v[j] = EMIT ? __builtin_nontemporal_load(vp + ii) : 0;
-                }
-#pragma unroll
-                for (int j = 0; j < 8; ++j) e[j] = live[j] ? (uint32_t)tslice[e[j]] : 0u;
-                if (EMIT) {
-                    emit_matches(e, v, live, amin, &base, out_v, out_a);
-                } else {
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) matches += (uint32_t)popc64(__ballot(live[j] && e[j] != 0u));
-                }
-            }
-            if (!EMIT && lane == 0) counts[s] = matches;
-        }
-        sb = se;
-    }
-}
-
-// Exact region sizes for phase A of the materialising join: the same tile ->
-// workgroup assignment as k_slice_partition, keys only (16-B loads), per-wave
-// LDS counters; counts[b * grid + wg] (slice-major slots).
-__global__ __launch_bounds__(kSliceBlock) void k_slice_count(const int64_t *__restrict__ key, int64_t kmin, uint64_t range,
-                                                             int64_t n_tiles, int F, uint32_t *__restrict__ counts) {
-    constexpr int W = kSliceBlock / 64;
-    __shared__ uint32_t cnt[W][kSliceMaxF];
-    const int tid = threadIdx.x, wave = tid >> 6;
-    for (int i = tid; i < W * kSliceMaxF; i += kSliceBlock) (&cnt[0][0])[i] = 0;
-    __syncthreads();
-    for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-        const int64_t base = tile * kSliceTile;
-        v2i64 kk[kSliceTile / (2 * kSliceBlock)];
-#pragma unroll
-        for (int q = 0; q < kSliceTile / (2 * kSliceBlock); ++q)
-            kk[q] = __builtin_nontemporal_load((const v2i64 *)(key + base + 2 * ((int64_t)q * kSliceBlock + tid)));
-#pragma unroll
-        for (int q = 0; q < kSliceTile / (2 * kSliceBlock); ++q)
-#pragma unroll
-            for (int x = 0; x < 2; ++x) {
-                const uint64_t o = (uint64_t)kk[q][x] - (uint64_t)kmin;
-                if (o < range) atomicAdd(&cnt[wave][(uint32_t)(o >> kSliceBits)], 1u);
-            }
-    }
-    __syncthreads();
-    for (int b = tid; b < F; b += kSliceBlock) {
-        uint32_t c = 0;
-#pragma unroll
-        for (int w = 0; w < W; ++w) c += cnt[w][b];
-        counts[(uint64_t)b * gridDim.x + blockIdx.x] = c;
-    }
-}
-
-// Phase B of the exact-layout join: the probe payload already sits at its
-// output position (phase A wrote it into the output column), so each item only
-// needs the build payload written beside it: read the 16-bit key offset, look
-// it up in the LDS slice, store a.  Items without a match are counted (a
-// non-zero count sends the host to the compacting two-pass emit).
-__global__ __launch_bounds__(kSliceBlock) void k_slice_join_inplace(SliceRegions rg, int nreg, HashTable t, int64_t amin,
-                                                                    int64_t *__restrict__ out_a,
-                                                                    unsigned long long *__restrict__ misses) {
-    __shared__ __attribute__((aligned(16))) uint16_t tslice[kSliceKeys];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    constexpr int W = kSliceBlock / 64;
-    const int F = rg.F;
-    const int64_t T = (int64_t)F * nreg;
-    const int64_t s0 = (int64_t)blockIdx.x * T / gridDim.x, s1 = (int64_t)(blockIdx.x + 1) * T / gridDim.x;
-    uint32_t miss = 0;
-    for (int64_t sb = s0; sb < s1;) {
-        const int b = (int)(sb / nreg);
-        const int64_t se = std::min<int64_t>(s1, (int64_t)(b + 1) * nreg);
-        __syncthreads();
-        load_slice(tslice, t, b, tid);
-        __syncthreads();
-        for (int64_t s = sb + wave; s < se; s += W) {
-            const uint64_t reg = (uint64_t)(s - (int64_t)b * nreg) * F + b;
-            const uint32_t n_r = rg.count[reg];
-            const uint64_t rb = rg.rbase[s];
-            const uint16_t *kp = rg.key + rb;
-            int64_t *ap = out_a + rb;
-            // the next 1024 keys are loaded before this batch's lookups and stores
-            uint32_t e[16];
-#pragma unroll
-            for (int j = 0; j < 16; ++j) {
-                const uint32_t i = j * 64 + lane;
-                e[j] = __builtin_nontemporal_load(kp + (i < n_r ? i : 0u));
-            }
-            for (uint32_t i0 = 0; i0 < n_r; i0 += 64 * 16) {
-                uint32_t en[16];
-                const uint32_t i1 = i0 + 64 * 16;
-#pragma unroll
-                for (int j = 0; j < 16; ++j) {
-                    const uint32_t i = i1 + j * 64 + lane;
-                    en[j] = __builtin_nontemporal_load(kp + (i < n_r ? i : 0u));
-                }
-#pragma unroll
-                for (int j = 0; j < 16; ++j) {
-                    const uint32_t i = i0 + j * 64 + lane;
-                    if (i < n_r) {
-                        const uint32_t x = tslice[e[j]];
-                        miss += x == 0u;
-                        __builtin_nontemporal_store((int64_t)(x - 1u) + amin, ap + i);
-                    }
-                }
-#pragma unroll
-                for (int j = 0; j < 16; ++j) e[j] = en[j];
-            }
-        }
-        sb = se;
-    }
-    const uint64_t m = wave_sum_u64(miss);
-    if (lane == 0 && m) atomicAdd(misses, (unsigned long long)m);
-}
-
-// ragged tail (< one 8192-row tile): probe the u16 table directly and append
-// after the regions' rows (a few waves: one atomic each per 512 rows)
-__global__ __launch_bounds__(kBlock) void k_slice_join_tail(const int64_t *__restrict__ key, const int64_t *__restrict__ val,
-                                                            int64_t n, HashTable t, int64_t amin, int64_t *__restrict__ out_v,
-                                                            int64_t *__restrict__ out_a, unsigned long long *counter) {
-    const int lane = threadIdx.x & 63;
-    for (int64_t i0 = (int64_t)blockIdx.x * blockDim.x * 8 + (threadIdx.x & ~63) * 8; i0 < n;
-         i0 += (int64_t)gridDim.x * blockDim.x * 8) {
-        uint32_t e[8];
-        int64_t v[8];
-        bool live[8];
-        uint32_t total = 0;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const int64_t i = i0 + j * 64 + lane;
-            live[j] = i < n;
-            e[j] = 0u;
-            v[j] = 0;
-            if (live[j]) {
-                const uint64_t o = (uint64_t)key[i] - (uint64_t)t.kmin;
-                if (o < t.range) e[j] = t.payload16[o];
-                v[j] = val[i];
-            }
-            total += (uint32_t)popc64(__ballot(live[j] && e[j] != 0u));
-        }
-        unsigned long long b = 0;
-        if (lane == 0 && total) b = atomicAdd(counter, (unsigned long long)total);
-        uint64_t base = __shfl(b, 0, 64);
-        emit_matches(e, v, live, amin, &base, out_v, out_a);
-    }
-}
-
 // ---- single-pass GROUP BY on one key: LDS hash table per workgroup ----------------------
 // Each workgroup aggregates its rows into an LDS open-addressing table keyed by
 // the key's 64-bit payload (ints sign-extended, floats as bits); rows whose key
@@ -2239,28 +1408,6 @@ __global__ void k_group_nonempty(const uint64_t *states, int64_t G, uint32_t *fl
         flags[g] = states[g] != 0;
 }
 
-struct OutCol {
-    void *values;
-    uint32_t *validity;  // nullptr when never null
-    int32_t dtype;
-    int32_t _pad;
-};
-struct OutCols {
-    OutCol c[kMaxGroupKeys + kMaxAggs];
-};
-
-__device__ __forceinline__ void write_value(const OutCol &o, int64_t p, int64_t payload, bool valid) {
-    if (o.validity && valid) atomicOr(&o.validity[p >> 5], 1u << (p & 31));
-    switch (o.dtype) {
-        case QEH_DT_BOOL:
-            if (payload & 1) atomicOr(&((uint32_t *)o.values)[p >> 5], 1u << (p & 31));
-            break;
-        case QEH_DT_INT32: ((int32_t *)o.values)[p] = (int32_t)payload; break;
-        case QEH_DT_FLOAT32: ((float *)o.values)[p] = (float)as_f64(payload); break;
-        default: ((int64_t *)o.values)[p] = payload; break;  // INT64, FLOAT64 bits
-    }
-}
-
 __global__ void k_finalize(const uint64_t *__restrict__ states, int64_t G, const uint64_t *__restrict__ pos,
                            KeyCols keys, const uint32_t *__restrict__ rep_row, AggSpecs specs, OutCols outs) {
     for (int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; g < G; g += (int64_t)gridDim.x * blockDim.x) {
@@ -2304,78 +1451,8 @@ __global__ void k_finalize(const uint64_t *__restrict__ states, int64_t G, const
     }
 }
 
-// After phase B (shard copies folded): one workgroup compacts the non-empty group slots, writes the
-// output keys, aggregates and validity words (zeroed here first) and the group count (*total).
-__global__ __launch_bounds__(1024) void k_fused_finish(const uint64_t *__restrict__ states, int64_t G, KeyCols keys,
-                                                       const uint32_t *__restrict__ rep, AggSpecs specs, OutCols outs,
-                                                       uint64_t *__restrict__ total) {
-    __shared__ uint32_t pos[kSliceStateWords];
-    __shared__ uint32_t vbits[kMaxGroupKeys + kMaxAggs][kSliceStateWords / 32];  // validity, built in LDS
-    __shared__ uint32_t wsum[16];
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int nout = keys.n + specs.n;
-    const int64_t vwords = (G + 31) / 32;
-    for (int c = 0; c < nout; ++c)
-        for (int64_t w = t; w < vwords; w += blockDim.x) vbits[c][w] = 0u;
-    const int64_t per = (G + 1023) / 1024, g0 = (int64_t)t * per, g1 = g0 + per < G ? g0 + per : G;
-    uint32_t c = 0;
-    for (int64_t g = g0; g < g1; ++g) c += states[g] != 0;
-    const uint32_t incl = wave_incl_scan(c);
-    if (lane == 63) wsum[wave] = incl;
-    __syncthreads();
-    uint32_t base = incl - c, all = 0;
-    for (int w = 0; w < 16; ++w) {
-        base += w < wave ? wsum[w] : 0u;
-        all += wsum[w];
-    }
-    for (int64_t g = g0; g < g1; ++g) {
-        pos[g] = base;
-        base += states[g] != 0;
-    }
-    if (t == 0) *total = all;
-    __syncthreads();  // validity bits zeroed, positions known
-    // values by plain stores, validity bits in LDS (written out once below)
-    auto put = [&](int c, int64_t p, int64_t payload, bool valid) {
-        OutCol o = outs.c[c];
-        if (o.validity && valid) atomicOr(&vbits[c][p >> 5], 1u << (p & 31));
-        o.validity = nullptr;
-        write_value(o, p, payload, true);
-    };
-    for (int64_t g = t; g < G; g += blockDim.x) {
-        const uint64_t rows = states[g];
-        if (!rows) continue;
-        const int64_t p = pos[g];
-        for (int k = 0; k < keys.n; ++k) {
-            const int64_t r = rep[g];
-            put(k, p, load_i64(keys.c[k], r), col_valid(keys.c[k], r));
-        }
-        for (int a = 0; a < specs.n; ++a) {
-            const AggSpec sp = specs.a[a];
-            const uint64_t cnt = sp.cnt_slot ? states[(int64_t)sp.cnt_slot * G + g] : rows;
-            const int64_t v = sp.kind == AK_COUNT ? 0 : (int64_t)states[(int64_t)sp.val_slot * G + g];
-            const int o = keys.n + a;
-            const bool i32 = sp.in_type == QEH_DT_INT32;
-            const bool flt = sp.in_type == QEH_DT_FLOAT32 || sp.in_type == QEH_DT_FLOAT64;
-            switch (sp.func) {
-                case QEH_AGG_COUNT: put(o, p, (int64_t)cnt, true); break;
-                case QEH_AGG_SUM: put(o, p, i32 ? (int64_t)(int32_t)v : v, cnt != 0); break;
-                case QEH_AGG_AVG: {
-                    double sm = flt ? as_f64(v) : (double)(i32 ? (int64_t)(int32_t)v : v);
-                    put(o, p, f64_bits(cnt ? sm / (double)cnt : 0.0), cnt != 0);
-                    break;
-                }
-                default: put(o, p, flt ? f64_bits(f64_from_order_key(v)) : v, cnt != 0); break;
-            }
-        }
-    }
-    __syncthreads();
-    for (int c = 0; c < nout; ++c)
-        if (outs.c[c].validity)
-            for (int64_t w = t; w < vwords; w += blockDim.x) outs.c[c].validity[w] = vbits[c][w];
-}
-
 // ---- host helpers ----------------------------------------------------------------------
-static int agg_output_type(int func, int in_type) {
+int agg_output_type(int func, int in_type) {
     switch (func) {
         case QEH_AGG_COUNT: return QEH_DT_INT64;
         case QEH_AGG_SUM: return (in_type == QEH_DT_FLOAT32 || in_type == QEH_DT_FLOAT64) ? QEH_DT_FLOAT64 : QEH_DT_INT64;
@@ -2433,12 +1510,6 @@ static int plan_aggs(const qeh_agg *aggs, int n_aggs, const qeh_column *inputs, 
     return QEH_OK;
 }
 
-struct PredPlan {
-    int mode = PM_NONE;
-    PredTerms terms{};
-    DevProgram prog{};
-};
-
 static int plan_predicate(const qeh_expr *pred, const int32_t *dtypes, int n_cols, PredPlan *pp) {
     pp->mode = PM_NONE;
     if (!pred || pred->n_nodes == 0) return QEH_OK;
@@ -2469,72 +1540,8 @@ static ColRef advance(ColRef c, int64_t rows) {
     return c;
 }
 
-static bool fast_col_ok(const ColRef &c) {
-    return (c.dtype == QEH_DT_INT64 || c.dtype == QEH_DT_FLOAT64) && c.validity == nullptr &&
-           ((uintptr_t)c.values & 15) == 0;
-}
-
-static int fast_nt_mode() {
-    static int m = -1;
-    if (m < 0) {
-        const char *e = std::getenv("QEH_NT_LOADS");  // non-temporal fact-column loads (default on: -4%)
-        m = (e && e[0] == '0') ? 0 : 1;
-    }
-    return m;
-}
-
-// The fused probe's fast path: returns true when it launched (full tiles by
-// k_join_agg_fast, the ragged tail by the generic kernel).
-// Eligibility of the specialised probe kernels; fills the kernel's view.
-// `key_col`: the column read as FastIn::key (join probe key or group key).
-static bool fast_cols_eligible(const ColSet &cols, const PredPlan &pp, int key_col, const AggSpecs &specs,
-                               FastIn *inp, int *nterms_out, int *nacol_out) {
-    if (pp.mode == PM_PROG || (pp.mode == PM_TERMS && pp.terms.n > 2)) return false;
-    if (!fast_col_ok(cols.c[key_col])) return false;
-    FastIn &in = *inp;
-    in = FastIn{};
-    in.key = (const int64_t *)cols.c[key_col].values;
-    const int nterms = pp.mode == PM_TERMS ? pp.terms.n : 0;
-    for (int i = 0; i < nterms; ++i) {
-        const ColRef &c = cols.c[pp.terms.t[i].col];
-        if (!fast_col_ok(c)) return false;
-        in.term[i] = (const int64_t *)c.values;
-        in.term_dt[i] = c.dtype;
-    }
-    int nacol = 0;
-    int acol_idx[2] = {-1, -1};
-    for (int a = 0; a < specs.n; ++a) {
-        const AggSpec &sp = specs.a[a];
-        if (sp.cnt_slot != 0) return false;
-        in.agg_colslot[a] = -1;
-        if (sp.kind == AK_COUNT) continue;
-        int slot = -1;
-        for (int c = 0; c < nacol; ++c)
-            if (acol_idx[c] == sp.col) slot = c;
-        if (slot < 0) {
-            if (nacol == 2) return false;
-            if (!fast_col_ok(cols.c[sp.col])) return false;
-            acol_idx[nacol] = sp.col;
-            in.acol[nacol] = (const int64_t *)cols.c[sp.col].values;
-            slot = nacol++;
-        }
-        in.agg_colslot[a] = slot;
-    }
-    *nterms_out = nterms;
-    *nacol_out = nacol;
-    return true;
-}
-
-static bool fast_eligible(const ColSet &cols, const PredPlan &pp, const GidSource &src, const AggSpecs &specs,
-                          FastIn *inp, int *nterms_out, int *nacol_out) {
-    if (!src.jt.unique) return false;
-    if (cols.c[src.key_col].dtype != QEH_DT_INT64) return false;
-    return fast_cols_eligible(cols, pp, src.key_col, specs, inp, nterms_out, nacol_out);
-}
-
-static void launch_tail(qeh_ctx *ctx, const ColSet &cols, int64_t n, int64_t done, const PredPlan &pp,
-                        const GidSource &src, const AggSpecs &specs, int64_t G, uint64_t *states, uint32_t *err,
-                        size_t lds_bytes) {
+void launch_tail(qeh_ctx *ctx, const ColSet &cols, int64_t n, int64_t done, const PredPlan &pp, const GidSource &src,
+                 const AggSpecs &specs, int64_t G, uint64_t *states, uint32_t *err, size_t lds_bytes) {
     if (done >= n) return;
     ColSet tail = cols;
     for (int i = 0; i < cols.n; ++i) tail.c[i] = advance(cols.c[i], done);
@@ -2545,101 +1552,13 @@ static void launch_tail(qeh_ctx *ctx, const ColSet &cols, int64_t n, int64_t don
                              err);
 }
 
-static uint64_t table_bytes(const HashTable &t);
-
-// The bucket-range partitioned probe (k_bp_part + chunk_lists + k_bp_probe) for a BUCKET table past
-// the Infinity Cache's comfortable share; false when it does not apply (nothing launched).
-static bool try_bucket_parts(qeh_ctx *ctx, const FastIn &in, const PredPlan &pp, int nterms, int nacol,
-                             const AggSpecs &specs, const HashTable &t, int64_t G, int64_t n, uint64_t *states,
-                             size_t lds_bytes) {
-    // opt-in (QEH_BUCKET_PARTS=1): measured slower than the single pass at the sparse metric shape
-    // (P1 7.5-7.9 ms + P2 8.9 ms against 13.2 ms; profiles/r06/bucket_parts.txt) -- the probes hit the
-    // XCD's L2 (4.7e8 TCC hits, 1.1e8 misses) and still run at the single pass's ~56 G probes/s
-    if (t.kind != TK_BUCKET || nacol > 1 || !std::getenv("QEH_BUCKET_PARTS")) return false;
-    if (lds_bytes > 64 * 1024) return false;
-    const int cus = ctx->props.multiProcessorCount;
-    const int64_t n_tiles = (n + kBpTile - 1) / kBpTile;
-    const int grid1 = (int)std::max<int64_t>(1, std::min<int64_t>(2 * (int64_t)cus, n_tiles));
-    const uint64_t max_chunks = (uint64_t)(n + kBpChunk - 1) / kBpChunk + (uint64_t)grid1 * kBpP;
-    if (max_chunks >= (1ull << 24)) return false;
-    DevBuf keys, vals, tags, cnts, lists, ctr;
-    if (keys.alloc(ctx, max_chunks * kBpChunk * 8) != QEH_OK || (nacol && vals.alloc(ctx, max_chunks * kBpChunk * 8) != QEH_OK) ||
-        tags.alloc(ctx, max_chunks * 2) != QEH_OK || cnts.alloc(ctx, max_chunks * 2) != QEH_OK ||
-        lists.alloc(ctx, max_chunks * 4 + (kBpP + 1) * 4 + chunk_lists_work_words(kBpP) * 4) != QEH_OK ||
-        ctr.alloc(ctx, 4) != QEH_OK)
-        return false;
-    if (hipMemsetAsync(tags.p, 0xFF, max_chunks * 2, ctx->stream) != hipSuccess ||
-        hipMemsetAsync(ctr.p, 0, 4, ctx->stream) != hipSuccess)
-        return false;
-    const int acs = nacol ? 0 : -1;
-    KernelTimer kt(ctx, "bucket_parts");
-    const bool nt = fast_nt_mode() == 1;
-#define QEH_BP(NTV, NAV, NTB)                                                                                            \
-    hipLaunchKernelGGL((k_bp_part<NTV, NAV, NTB>), dim3(grid1), dim3(kBpBlock), 0, ctx->stream, in, pp.terms, n, acs,   \
-                       keys.as<uint64_t>(), vals.as<uint64_t>(), tags.as<uint16_t>(), cnts.as<uint16_t>(), ctr.as<uint32_t>())
-#define QEH_BP_NA(NTV, NTB)                  \
-    if (nacol == 0) QEH_BP(NTV, 0, NTB);     \
-    else QEH_BP(NTV, 1, NTB);
-#define QEH_BP_NT(NTB)                           \
-    if (nterms == 0) { QEH_BP_NA(0, NTB) }       \
-    else if (nterms == 1) { QEH_BP_NA(1, NTB) }  \
-    else { QEH_BP_NA(2, NTB) }
-    if (nt) { QEH_BP_NT(true) } else { QEH_BP_NT(false) }
-#undef QEH_BP_NT
-#undef QEH_BP_NA
-#undef QEH_BP
-    uint32_t *sbase = lists.as<uint32_t>() + max_chunks;
-    if (chunk_lists(ctx, tags.as<uint16_t>(), cnts.as<uint16_t>(), max_chunks, kBpP, sbase, lists.as<uint32_t>(),
-                    sbase + kBpP + 1) != QEH_OK)
-        return false;
-    const int grid2 = std::max(8, (2 * cus + 7) / 8 * 8);  // a multiple of 8: every XCD the same count
-    if (nacol)
-        hipLaunchKernelGGL(k_bp_probe<1>, dim3(grid2), dim3(kBpBlock), lds_bytes, ctx->stream, specs, in, t, G, sbase,
-                           lists.as<uint32_t>(), keys.as<uint64_t>(), vals.as<uint64_t>(), states);
-    else
-        hipLaunchKernelGGL(k_bp_probe<0>, dim3(grid2), dim3(kBpBlock), lds_bytes, ctx->stream, specs, in, t, G, sbase,
-                           lists.as<uint32_t>(), keys.as<uint64_t>(), vals.as<uint64_t>(), states);
-    // the pool buffers above must outlive the kernels
-    return hipStreamSynchronize(ctx->stream) == hipSuccess;
+void states_fold(qeh_ctx *ctx, uint64_t *states, int64_t Gs, const AggSpecs &specs) {
+    const int64_t words = (int64_t)specs.n_slots * Gs;
+    hipLaunchKernelGGL(k_states_fold, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, ctx->stream, states, Gs, specs);
 }
 
-static bool try_fast_join(qeh_ctx *ctx, const ColSet &cols, int64_t n, const PredPlan &pp, const GidSource &src,
-                          const AggSpecs &specs, int64_t G, uint64_t *states, uint32_t *err, size_t lds_bytes,
-                          int per_cu) {
-    if (std::getenv("QEH_NO_FAST")) return false;
-    FastIn in;
-    int nterms, nacol;
-    if (!fast_eligible(cols, pp, src, specs, &in, &nterms, &nacol)) return false;
-    if (try_bucket_parts(ctx, in, pp, nterms, nacol, specs, src.jt, G, n, states, lds_bytes)) return true;
-    const int64_t n_tiles = n / kFastTile;
-    if (n_tiles > 0) {
-        const int grid = grid_for(ctx, n_tiles * kFastTile, kFastTile, per_cu);
-        const bool nt = fast_nt_mode() == 1;
-#define QEH_FAST(NTV, NAV, NTB)                                                                                    \
-    hipLaunchKernelGGL((k_join_agg_fast<NTV, NAV, NTB>), dim3(grid), dim3(kBlock), lds_bytes, ctx->stream, in, pp.terms, \
-                       specs, src.jt, G, n_tiles, states)
-#define QEH_FAST_NA(NTV, NTB)                       \
-    if (nacol == 0) QEH_FAST(NTV, 0, NTB);          \
-    else if (nacol == 1) QEH_FAST(NTV, 1, NTB);     \
-    else QEH_FAST(NTV, 2, NTB);
-#define QEH_FAST_NT(NTB)                            \
-    if (nterms == 0) { QEH_FAST_NA(0, NTB) }        \
-    else if (nterms == 1) { QEH_FAST_NA(1, NTB) }   \
-    else { QEH_FAST_NA(2, NTB) }
-        if (nt) { QEH_FAST_NT(true) } else { QEH_FAST_NT(false) }
-#undef QEH_FAST_NT
-#undef QEH_FAST_NA
-#undef QEH_FAST
-    }
-    launch_tail(ctx, cols, n, n_tiles * kFastTile, pp, src, specs, G, states, err, lds_bytes);
-    return true;
-}
-
-static uint64_t table_bytes(const HashTable &t) {
-    if (t.kind == TK_DIRECT) return t.range * (t.payload16 ? 2 : 4);
-    if (t.kind == TK_PACKED) return (t.mask + 1) * 8;
-    if (t.kind == TK_BUCKET) return t.nbkt * 64;
-    return (t.mask + 1) * 16;
+void fill_i64(qeh_ctx *ctx, int grid, int block, int64_t *p, int64_t n, int64_t v) {
+    hipLaunchKernelGGL(k_fill_i64, dim3(grid), dim3(block), 0, ctx->stream, p, n, v);
 }
 
 // Phase A does not need the join table — only its key range — so the fused join-aggregate
@@ -2759,32 +1678,21 @@ static bool slice_regions(qeh_ctx *ctx, int64_t n_tiles, int grid, uint64_t F, i
 }
 
 // gid_table != nullptr: MODE 1 (group-range slices, `range` = groups)
-static void launch_slice_partition(qeh_ctx *ctx, const FastIn &in, const PredPlan &pp, int nterms, int nacol, int64_t kmin,
-                                   uint64_t range, int64_t n_tiles, int grid, const SliceRegions &rg_in, hipStream_t stream,
-                                   const HashTable *gid_table = nullptr, const SlicePlan *dplan = nullptr) {
-    const bool nt = fast_nt_mode() == 1;
+void launch_slice_partition(qeh_ctx *ctx, const FastIn &in, const PredPlan &pp, int nterms, int nacol, int64_t kmin,
+                            uint64_t range, int64_t n_tiles, int grid, const SliceRegions &rg_in, hipStream_t stream,
+                            const HashTable *gid_table, const SlicePlan *dplan, const char *timer) {
     SliceRegions rg = rg_in;
-    KernelTimer kta(ctx, "slice_partition", stream);
+    std::optional<KernelTimer> kta;
+    if (timer) kta.emplace(ctx, timer, stream);
     const HashTable t = gid_table ? *gid_table : HashTable{};
-#define QEH_SA(NTV, NAV, NTB)                                                                                        \
-    if (gid_table)                                                                                                   \
-        hipLaunchKernelGGL((k_slice_partition<NTV, NAV, NTB, 1>), dim3(grid), dim3(kSliceBlock), 0, stream, in,     \
-                           pp.terms, kmin, range, n_tiles, rg, t, nullptr);                                          \
-    else                                                                                                             \
-        hipLaunchKernelGGL((k_slice_partition<NTV, NAV, NTB>), dim3(grid), dim3(kSliceBlock), 0, stream, in,        \
-                           pp.terms, kmin, range, n_tiles, rg, t, dplan)
-#define QEH_SA_NA(NTV, NTB)                    \
-    if (nacol == 0) { QEH_SA(NTV, 0, NTB); }   \
-    else if (nacol == 1) { QEH_SA(NTV, 1, NTB); } \
-    else { QEH_SA(NTV, 2, NTB); }
-#define QEH_SA_NT(NTB)                         \
-    if (nterms == 0) { QEH_SA_NA(0, NTB) }     \
-    else if (nterms == 1) { QEH_SA_NA(1, NTB) } \
-    else { QEH_SA_NA(2, NTB) }
-    if (nt) { QEH_SA_NT(true) } else { QEH_SA_NT(false) }
-#undef QEH_SA_NT
-#undef QEH_SA_NA
-#undef QEH_SA
+    dispatch_fast(nterms, nacol, fast_nt_mode() == 1, [&](auto NTV, auto NAV, auto NTB) {
+        if (gid_table)
+            hipLaunchKernelGGL((k_slice_partition<NTV.value, NAV.value, NTB.value, 1>), dim3(grid), dim3(kSliceBlock), 0,
+                               stream, in, pp.terms, kmin, range, n_tiles, rg, t, nullptr);
+        else
+            hipLaunchKernelGGL((k_slice_partition<NTV.value, NAV.value, NTB.value>), dim3(grid), dim3(kSliceBlock), 0,
+                               stream, in, pp.terms, kmin, range, n_tiles, rg, t, dplan);
+    });
 }
 
 // Tiles per chunk of the chunked slice pipeline (QEH_SLICE_CHUNK_TILES; 0 = one pass).
@@ -2813,8 +1721,7 @@ static int slice_launch_dev(qeh_ctx *ctx, const ColSet &cols, int64_t n, const P
     hipStream_t side = n_tiles ? aux_stream(ctx) : nullptr;
     if (!side) return QEH_OK;
     *pi = SlicePlanIn{};
-    pi->min_bytes = 6ull << 20;
-    if (const char *e = std::getenv("QEH_SLICE_MIN_BYTES")) pi->min_bytes = std::strtoull(e, nullptr, 10);
+    pi->min_bytes = slice_min_bytes();
     pi->grid = (int)std::min<int64_t>(ctx->props.multiProcessorCount, n_tiles);
     pi->n_slots = specs.n_slots;
     pi->sparse_ok = direct_sparse_allowed() ? 1 : 0;
@@ -2961,9 +1868,7 @@ static int slice_prelaunch_ranges(qeh_ctx *ctx, const ColSet &cols, int64_t n, c
     const uint64_t range = (uint64_t)mx - (uint64_t)mn + 1ull;
     // the DIRECT rule of build_join_table, and the slice path's own limits
     if (!direct_table_ok(range, (uint64_t)cnt, (uint64_t)g_bound)) return QEH_OK;
-    uint64_t min_bytes = 6ull << 20;
-    if (const char *e = std::getenv("QEH_SLICE_MIN_BYTES")) min_bytes = std::strtoull(e, nullptr, 10);
-    if (range * 2 < min_bytes) return QEH_OK;
+    if (range * 2 < slice_min_bytes()) return QEH_OK;
     const uint64_t F = (range + kSliceKeys - 1) >> kSliceBits;
     if (F == 0 || F > (uint64_t)kSliceMaxF) return QEH_OK;
     // optionally leave CUs to the build on the main queue (QEH_SLICE_RESERVE_CUS): with one
@@ -3050,9 +1955,7 @@ static int try_slice_join(qeh_ctx *ctx, const ColSet &cols, int64_t n, const Pre
     const uint64_t F = (t.range + kSliceKeys - 1) >> kSliceBits;
     if (F == 0 || F > (uint64_t)kSliceMaxF) return 0;
     // below ~1.5 L2s the single pass's lookups mostly hit L2 and it wins
-    uint64_t min_bytes = 6ull << 20;
-    if (const char *e = std::getenv("QEH_SLICE_MIN_BYTES")) min_bytes = std::strtoull(e, nullptr, 10);
-    if (table_bytes(t) < min_bytes) return 0;
+    if (table_bytes(t) < slice_min_bytes()) return 0;
     // two aggregate columns: half tiles (SliceShape<2>)
     const int64_t tile_rows = nacol == 2 ? (int64_t)SliceShape<2>::TILE : (int64_t)kSliceTile;
     const int64_t n_tiles = n / tile_rows;
@@ -3199,9 +2102,7 @@ static int try_key_slices(qeh_ctx *ctx, const ColSet &cols, int64_t n, const Pre
     const int gridB = 8 * gpx * nw;
     const uint64_t F = (t.range + kSliceKeys - 1) >> kSliceBits;
     if (F == 0 || F > (uint64_t)kSliceMaxF) return 0;
-    uint64_t min_bytes = 6ull << 20;
-    if (const char *e = std::getenv("QEH_SLICE_MIN_BYTES")) min_bytes = std::strtoull(e, nullptr, 10);
-    if (table_bytes(t) < min_bytes) return 0;
+    if (table_bytes(t) < slice_min_bytes()) return 0;
     const int64_t n_tiles = n / kSliceTile;
     if (n_tiles == 0) return 0;
     const int grid = (int)std::min<int64_t>(ctx->props.multiProcessorCount, n_tiles);
@@ -3296,150 +2197,6 @@ static int try_gid_slices(qeh_ctx *ctx, const ColSet &cols, int64_t n, const Pre
     return 1;
 }
 
-int slice_join_materialise(qeh_ctx *ctx, const qeh_column &probe_key, const qeh_column &probe_val,
-                           const qeh_column &build_key, const qeh_column &build_val, qeh_column *out_probe,
-                           qeh_column *out_build, int64_t *out_rows) {
-    if (std::getenv("QEH_NO_SLICES")) return kSliceJoinNotEligible;
-    const ColRef pk = make_colref(probe_key), pv = make_colref(probe_val);
-    if (probe_key.dtype != QEH_DT_INT64 || !fast_col_ok(pk) || !fast_col_ok(pv)) return kSliceJoinNotEligible;
-    if (build_val.dtype != QEH_DT_INT64 || (build_val.validity && build_val.null_count != 0)) return kSliceJoinNotEligible;
-    if (build_key.validity && build_key.null_count != 0) return kSliceJoinNotEligible;
-    const int64_t n = probe_key.length;
-    const int64_t n_tiles = n / kSliceTile;
-    if (n_tiles == 0 || build_key.length == 0) return kSliceJoinNotEligible;
-    // build payload as a frame-of-reference u16: (a - amin) + 1 in the direct table
-    int64_t amin, amax, avalid;
-    QEH_TRY(column_minmax(ctx, build_val, &amin, &amax, &avalid));
-    if ((uint64_t)amax - (uint64_t)amin >= 0xFFFEull) return kSliceJoinNotEligible;
-    BuiltTable bt;
-    RowPayload rp;
-    rp.values = (const int64_t *)build_val.values + build_val.offset;
-    rp.bias = amin;
-    QEH_TRY(build_join_table(ctx, build_key, rp, (uint64_t)amax - (uint64_t)amin, &bt));
-    const HashTable &t = bt.t;
-    if (!t.unique || t.kind != TK_DIRECT || !t.payload16) return kSliceJoinNotEligible;
-    const uint64_t F = (t.range + kSliceKeys - 1) >> kSliceBits;
-    if (F == 0 || F > (uint64_t)kSliceMaxF) return kSliceJoinNotEligible;
-    uint64_t min_bytes = 6ull << 20;
-    if (const char *e = std::getenv("QEH_SLICE_MIN_BYTES")) min_bytes = std::strtoull(e, nullptr, 10);
-    if (table_bytes(t) < min_bytes) return kSliceJoinNotEligible;
-
-    // Exact region layout: a key-only count pass sizes every (workgroup, slice) region, so
-    // phase A writes the probe payload straight into the output column (slice-major, no
-    // gaps) and phase B only adds the build payload beside it.  When some probe rows have
-    // no match, the two-pass emit compacts the regions into fresh columns instead.
-    const int grid = (int)std::min<int64_t>(ctx->props.multiProcessorCount, n_tiles);
-    const uint64_t nreg = (uint64_t)grid * F;
-    const uint64_t T = nreg;  // region slots, slice-major
-    DevBuf kbuf, cbuf, counts, bases;
-    QEH_TRY(cbuf.alloc(ctx, nreg * 4 + 64));
-    QEH_TRY(counts.alloc(ctx, T * 4 + 16));
-    QEH_TRY(bases.alloc(ctx, T * 8 + 16));
-    FastIn in{};
-    in.key = (const int64_t *)pk.values;
-    in.acol[0] = (const int64_t *)pv.values;
-    in.agg_colslot[0] = 0;
-    uint64_t region_rows = 0;
-    {
-        KernelTimer kt(ctx, "join_probe");
-        hipLaunchKernelGGL(k_slice_count, dim3(grid), dim3(kSliceBlock), 0, ctx->stream, in.key, t.kmin, t.range, n_tiles,
-                           (int)F, counts.as<uint32_t>());
-        QEH_HIP(hipGetLastError());
-    }
-    QEH_TRY(exclusive_scan_u32(ctx, counts.as<uint32_t>(), bases.as<uint64_t>(), (int64_t)T, &region_rows));
-    QEH_TRY(kbuf.alloc(ctx, region_rows * 2 + 64));
-    SliceRegions rg{};
-    rg.key = kbuf.as<uint16_t>();
-    rg.count = cbuf.as<uint32_t>();
-    rg.overflow = rg.count + nreg;                                                                     // 4 B
-    unsigned long long *counter = (unsigned long long *)(cbuf.as<char>() + ((nreg * 4 + 15) & ~15ull));  // 8 B
-    unsigned long long *misses = counter + 1;                                                          // 8 B
-    rg.cap = 1ull << 62;  // exact regions never overflow
-    rg.F = (int32_t)F;
-    rg.rbase = bases.as<uint64_t>();
-    QEH_HIP(hipMemsetAsync(rg.overflow, 0, 4, ctx->stream));
-    QEH_HIP(hipMemsetAsync(counter, 0, 16, ctx->stream));
-    QEH_TRY(alloc_column(ctx, probe_val.dtype, n, false, out_probe));
-    int st = alloc_column(ctx, QEH_DT_INT64, n, false, out_build);
-    if (st != QEH_OK) {
-        qeh_column_release(ctx, out_probe);
-        return st;
-    }
-    rg.val = (int64_t *)out_probe->values;
-    PredTerms none{};
-    const bool nt = fast_nt_mode() == 1;
-    int64_t *oa = (int64_t *)out_build->values;
-    const int gridB = ctx->props.multiProcessorCount;
-    {
-        KernelTimer kt(ctx, "join_probe");
-        if (nt)
-            hipLaunchKernelGGL((k_slice_partition<0, 1, true>), dim3(grid), dim3(kSliceBlock), 0, ctx->stream, in, none,
-                               t.kmin, t.range, n_tiles, rg, HashTable{}, nullptr);
-        else
-            hipLaunchKernelGGL((k_slice_partition<0, 1, false>), dim3(grid), dim3(kSliceBlock), 0, ctx->stream, in, none,
-                               t.kmin, t.range, n_tiles, rg, HashTable{}, nullptr);
-        hipLaunchKernelGGL(k_slice_join_inplace, dim3(gridB), dim3(kSliceBlock), 0, ctx->stream, rg, grid, t, amin, oa,
-                           misses);
-        if (hipGetLastError() != hipSuccess) st = fail(QEH_E_HIP, "slice join launch failed");
-    }
-    uint64_t nmiss = 0;
-    if (st == QEH_OK) st = read_small(ctx, &nmiss, misses, 8);
-    qeh_column cv = *out_probe, ca = *out_build;  // the columns the tail appends to
-    if (st == QEH_OK && nmiss != 0) {
-        // some probe rows have no match: compact the regions (read from the first output
-        // column) into fresh columns with the two-pass emit
-        qeh_column cv2{}, ca2{};
-        DevBuf counts2, bases2;
-        st = alloc_column(ctx, probe_val.dtype, n, false, &cv2);
-        if (st == QEH_OK) st = alloc_column(ctx, QEH_DT_INT64, n, false, &ca2);
-        if (st == QEH_OK) st = counts2.alloc(ctx, T * 4 + 16);
-        if (st == QEH_OK) st = bases2.alloc(ctx, T * 8 + 16);
-        if (st == QEH_OK) {
-            KernelTimer kt(ctx, "join_probe");
-            hipLaunchKernelGGL((k_slice_join_b<false>), dim3(gridB), dim3(kSliceBlock), 0, ctx->stream, rg, grid, t, amin,
-                               counts2.as<uint32_t>(), nullptr, nullptr, nullptr);
-        }
-        if (st == QEH_OK) st = exclusive_scan_u32(ctx, counts2.as<uint32_t>(), bases2.as<uint64_t>(), (int64_t)T, &region_rows);
-        if (st == QEH_OK) {
-            KernelTimer kt(ctx, "join_probe");
-            hipLaunchKernelGGL((k_slice_join_b<true>), dim3(gridB), dim3(kSliceBlock), 0, ctx->stream, rg, grid, t, amin,
-                               nullptr, bases2.as<uint64_t>(), (int64_t *)cv2.values, (int64_t *)ca2.values);
-            if (hipGetLastError() != hipSuccess) st = fail(QEH_E_HIP, "slice join launch failed");
-        }
-        if (st == QEH_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) st = fail(QEH_E_HIP, "slice join sync failed");
-        if (st == QEH_OK) {
-            qeh_column_release(ctx, out_probe);
-            qeh_column_release(ctx, out_build);
-            *out_probe = cv = cv2;
-            *out_build = ca = ca2;
-        } else {
-            if (cv2.values) qeh_column_release(ctx, &cv2);
-            if (ca2.values) qeh_column_release(ctx, &ca2);
-        }
-    }
-    if (st == QEH_OK) {
-        KernelTimer kt(ctx, "join_probe");
-        const int64_t done = n_tiles * kSliceTile;
-        hipLaunchKernelGGL(k_fill_i64, dim3(1), dim3(1), 0, ctx->stream, (int64_t *)counter, (int64_t)1, (int64_t)region_rows);
-        if (done < n)
-            hipLaunchKernelGGL(k_slice_join_tail, dim3(grid_for(ctx, n - done, kBlock * 8, 2)), dim3(kBlock), 0, ctx->stream,
-                               in.key + done, in.acol[0] + done, n - done, t, amin, (int64_t *)cv.values,
-                               (int64_t *)ca.values, counter);
-        if (hipGetLastError() != hipSuccess) st = fail(QEH_E_HIP, "slice join launch failed");
-    }
-    uint64_t rows = 0;
-    if (st == QEH_OK) st = read_small(ctx, &rows, counter, 8);
-    if (st != QEH_OK) {
-        qeh_column_release(ctx, out_probe);
-        qeh_column_release(ctx, out_build);
-        return st;
-    }
-    out_probe->length = (int64_t)rows;
-    out_build->length = (int64_t)rows;
-    *out_rows = (int64_t)rows;
-    return QEH_OK;
-}
-
 // Fast single-key GROUP BY (k_group_agg_fast) over the full tiles, generic
 // LDS-hash kernel over the ragged tail.  False when not eligible.
 static bool lds_group_fast(qeh_ctx *ctx, const ColSet &cols, int64_t n, const PredPlan &pp, const GidSource &src,
@@ -3461,26 +2218,14 @@ static bool lds_group_fast(qeh_ctx *ctx, const ColSet &cols, int64_t n, const Pr
     if (n_tiles > 0) {
         const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(wide ? 2 : 8, (160 * 1024) / shm));
         const int grid = grid_for(ctx, n_tiles * tile_rows, (int)tile_rows, per_cu);
-        const bool nt = fast_nt_mode() == 1;
-#define QEH_GF(NTV, NAV, NTB)                                                                                            \
-    if (wide)                                                                                                            \
-        hipLaunchKernelGGL((k_group_agg_fast<NTV, NAV, NTB, 1024>), dim3(grid), dim3(1024), shm, ctx->stream, in,        \
-                           pp.terms, specs, src.gt, lcap, G, n_tiles, states);                                          \
-    else                                                                                                                 \
-        hipLaunchKernelGGL((k_group_agg_fast<NTV, NAV, NTB>), dim3(grid), dim3(kBlock), shm, ctx->stream, in, pp.terms, \
-                           specs, src.gt, lcap, G, n_tiles, states)
-#define QEH_GF_NA(NTV, NTB)                       \
-    if (nacol == 0) QEH_GF(NTV, 0, NTB);          \
-    else if (nacol == 1) QEH_GF(NTV, 1, NTB);     \
-    else QEH_GF(NTV, 2, NTB);
-#define QEH_GF_NT(NTB)                            \
-    if (nterms == 0) { QEH_GF_NA(0, NTB) }        \
-    else if (nterms == 1) { QEH_GF_NA(1, NTB) }   \
-    else { QEH_GF_NA(2, NTB) }
-        if (nt) { QEH_GF_NT(true) } else { QEH_GF_NT(false) }
-#undef QEH_GF_NT
-#undef QEH_GF_NA
-#undef QEH_GF
+        dispatch_fast(nterms, nacol, fast_nt_mode() == 1, [&](auto NTV, auto NAV, auto NTB) {
+            if (wide)
+                hipLaunchKernelGGL((k_group_agg_fast<NTV.value, NAV.value, NTB.value, 1024>), dim3(grid), dim3(1024), shm,
+                                   ctx->stream, in, pp.terms, specs, src.gt, lcap, G, n_tiles, states);
+            else
+                hipLaunchKernelGGL((k_group_agg_fast<NTV.value, NAV.value, NTB.value>), dim3(grid), dim3(kBlock), shm,
+                                   ctx->stream, in, pp.terms, specs, src.gt, lcap, G, n_tiles, states);
+        });
     }
     const int64_t done = n_tiles * tile_rows;
     if (done < n) {
@@ -4361,233 +3106,45 @@ extern "C" int qeh_join_filter_aggregate_table_lanes_async(qeh_ctx *ctx, const q
                                        0, n_groups, QEH_DT_INT64, aggs, n_aggs, nullptr, nullptr, &g, lanes, dev_status);
 }
 
-// ---- the fused pipeline (one bounded integer group key, unique Int64 build keys) ----------------
-// Everything on the main queue, one host round trip per query (the status words after the finalize):
-//   build key / group key min-max -> k_fused_plan (slice shape, group slots, status words zeroed)
-//   -> states zeroed -> phase A (prologue: output group keys and the build rows grouped by slice into
-//   per-(workgroup, slice) regions, 4 B each; then the probe rows with EARLY loads and the ragged tail
-//   as a partial last tile) -> phase B (each slice's entries built in LDS from its build rows,
-//   duplicate keys flagged) -> fold / compact / finalize.
-// Returns kFusedNotEligible when the shape does not qualify (checked on the host) or the device plan,
-// a region overflow or a duplicate build key rejected the run (outputs released): the caller runs
-// the general path.
-constexpr int kFusedNotEligible = -4;
+namespace qeh {
 
-static void launch_slice_partition_early(qeh_ctx *ctx, const FastIn &in, const PredPlan &pp, int nterms, int nacol,
-                                         int64_t n_tiles, int64_t tail_rows, int grid, const SliceRegions &rg,
-                                         const SlicePlan *dplan, const FusedPro &fp) {
-    const bool nt = fast_nt_mode() == 1;
+// ---- phases A and B for the fused pipeline (k_agg_fused.hip) and the items forms below ----
+void launch_slice_partition_early(qeh_ctx *ctx, const FastIn &in, const PredPlan &pp, int nterms, int nacol,
+                                  int64_t n_tiles, int64_t tail_rows, int grid, const SliceRegions &rg,
+                                  const SlicePlan *dplan, const FusedPro &fp) {
     KernelTimer kta(ctx, "slice_partition");
     const HashTable t{};
-#define QEH_SE(NTV, NAV, NTB)                                                                                            \
-    hipLaunchKernelGGL((k_slice_partition<NTV, NAV, NTB, 0, true>), dim3(grid), dim3(kSliceBlock), 0, ctx->stream, in,   \
-                       pp.terms, 0, 0, n_tiles, rg, t, dplan, tail_rows, fp)
-#define QEH_SE_NA(NTV, NTB)                      \
-    if (nacol == 0) { QEH_SE(NTV, 0, NTB); }      \
-    else if (nacol == 1) { QEH_SE(NTV, 1, NTB); } \
-    else { QEH_SE(NTV, 2, NTB); }
-#define QEH_SE_NT(NTB)                          \
-    if (nterms == 0) { QEH_SE_NA(0, NTB) }      \
-    else if (nterms == 1) { QEH_SE_NA(1, NTB) } \
-    else { QEH_SE_NA(2, NTB) }
-    if (nt) { QEH_SE_NT(true) } else { QEH_SE_NT(false) }
-#undef QEH_SE_NT
-#undef QEH_SE_NA
-#undef QEH_SE
+    dispatch_fast(nterms, nacol, fast_nt_mode() == 1, [&](auto NTV, auto NAV, auto NTB) {
+        hipLaunchKernelGGL((k_slice_partition<NTV.value, NAV.value, NTB.value, 0, true>), dim3(grid), dim3(kSliceBlock), 0,
+                           ctx->stream, in, pp.terms, 0, 0, n_tiles, rg, t, dplan, tail_rows, fp);
+    });
 }
 
-static int fused_join_filter_aggregate(qeh_ctx *ctx, const ColSet &cols, int64_t n, const PredPlan &pp,
-                                       const AggSpecs &specs_in, int key_col, const qeh_column &bk, const qeh_column &gk,
-                                       qeh_column *out_keys, qeh_column *out_aggs, int64_t *out_groups) {
-    if (std::getenv("QEH_NO_FUSED") || std::getenv("QEH_NO_SLICES")) return kFusedNotEligible;
-    const size_t timing_mark = ctx->timing_pending.size();
-    const bool bk_nulls = bk.validity && bk.null_count != 0, gk_nulls = gk.validity && gk.null_count != 0;
-    if (bk.dtype != QEH_DT_INT64 || bk_nulls || (gk.dtype != QEH_DT_INT64 && gk.dtype != QEH_DT_INT32) || gk_nulls)
-        return kFusedNotEligible;
-    const int64_t nd = bk.length;
-    if (nd <= 0 || nd >= ((int64_t)1 << 32) || gk.length != nd) return kFusedNotEligible;
-    FastIn in;
-    int nterms, nacol;
-    if (!fast_cols_eligible(cols, pp, key_col, specs_in, &in, &nterms, &nacol) || nacol > 2 ||
-        (nacol == 2 && std::getenv("QEH_NO_FUSED_AGG2")))
-        return kFusedNotEligible;
-    // phase A: one 1024-thread workgroup per CU (two aggregate columns: 18-B items, half tiles)
-    const int64_t tile_rows = nacol == 2 ? (int64_t)SliceShape<2, true>::TILE
-                                         : (nacol ? SliceShape<1, true>::TILE : SliceShape<0, true>::TILE);
-    const int chunk = nacol == 2 ? SliceShape<2, true>::CH : (nacol ? SliceShape<1, true>::CH : SliceShape<0, true>::CH);
-    const int64_t n_tiles = n / tile_rows, tail = n - n_tiles * tile_rows;
-    if (n_tiles == 0) return kFusedNotEligible;
-    AggSpecs specs = specs_in;
-    const int64_t g_cap = std::min<int64_t>(kSliceStateWords / std::max(specs.n_slots, 1), 0xFFFE);
-    const int64_t Gs = g_cap;  // states and outputs for every possible slot; empty slots are dropped
-    // one copy of the states: phase B folds each slice's LDS states into them once per workgroup, so
-    // same-address contention is low and the shard fold launch is not worth its place in the chain
-    // (A/B on one box, profiles/r04/ab_early_shape.txt); QEH_FUSED_SHARDS=1 restores the copies
-    specs.shards = 1;
-    if (std::getenv("QEH_FUSED_SHARDS"))
-        while (specs.shards < 64 && (size_t)specs.n_slots * Gs * 8 * specs.shards * 2 <= (8u << 20)) specs.shards *= 2;
-    const int64_t n_all = n_tiles + (tail ? 1 : 0);
-    const int grid = (int)std::min<int64_t>({(int64_t)ctx->props.multiProcessorCount, n_all,
-                                             (int64_t)kMaxSliceGrid});
-    const uint64_t tiles_per_wg = (uint64_t)((n_all + grid - 1) / grid);
-
-    DevBuf mm, plan, ditems, dcount, kbuf, vbuf, vbuf2, cbuf, states, errw, gkeys, rep;
-    SlicePlanIn pi{};
-    pi.min_bytes = 6ull << 20;
-    if (const char *e = std::getenv("QEH_SLICE_MIN_BYTES")) pi.min_bytes = std::strtoull(e, nullptr, 10);
-    pi.grid = grid;
-    pi.n_slots = specs.n_slots;
-    pi.sparse_ok = direct_sparse_allowed() ? 1 : 0;
-    pi.chunk = chunk;
-    pi.alloc_items = tiles_per_wg * grid * (uint64_t)tile_rows * 5 / 4 + (uint64_t)grid * kSliceMaxF * (256 + 2 * chunk);
-    // build rows: uniform keys over the slices, +25 %, and per-region slack
-    const uint64_t dim_items = (uint64_t)nd * 5 / 4 + (uint64_t)grid * kSliceMaxF * 64;
-    if (dim_items >= (1ull << 32)) return kFusedNotEligible;  // phase B's region bases are 32-bit
-    const uint64_t nreg_max = (uint64_t)grid * kSliceMaxF;
-    QEH_TRY(mm.alloc(ctx, sizeof(MinMax) * 2 * (size_t)minmax_partials_max_blocks(ctx) + 16));  // the partials
-    QEH_TRY(plan.alloc(ctx, sizeof(FusedPlan)));
-    QEH_TRY(ditems.alloc(ctx, dim_items * 4 + 64));
-    QEH_TRY(dcount.alloc(ctx, nreg_max * 4 + 64));
-    QEH_TRY(kbuf.alloc(ctx, pi.alloc_items * 2 + 64));
-    if (nacol) QEH_TRY(vbuf.alloc(ctx, pi.alloc_items * 8 + 64));
-    if (nacol > 1) QEH_TRY(vbuf2.alloc(ctx, pi.alloc_items * 8 + 64));
-    QEH_TRY(cbuf.alloc(ctx, nreg_max * 4 + 64));
-    QEH_TRY(states.alloc(ctx, (size_t)specs.shards * specs.n_slots * Gs * 8));
-    // status words (zeroed by k_fused_plan): [0] kernel error bits, [1] region overflow, [2..3] groups,
-    // [4] duplicate build key, [5] the device plan's verdict
-    QEH_TRY(errw.alloc(ctx, 32));
-    QEH_TRY(gkeys.alloc(ctx, (size_t)Gs * 8));
-    QEH_TRY(rep.alloc(ctx, (size_t)Gs * 4));
-    uint32_t *st = errw.as<uint32_t>();
-    SliceRegions rg{};
-    rg.key = kbuf.as<uint16_t>();
-    rg.val = nacol ? vbuf.as<int64_t>() : nullptr;
-    rg.val2 = nacol > 1 ? vbuf2.as<int64_t>() : nullptr;
-    rg.count = cbuf.as<uint32_t>();
-    rg.overflow = st + 1;
-    FusedPlan *dplan = plan.as<FusedPlan>();
-    {
-        KernelTimer kt(ctx, "fused_build");
-        const qeh_column both[2] = {bk, gk};
-        int nb = 0;
-        QEH_TRY(columns_minmax_partials(ctx, both, 2, mm.as<MinMax>(), &nb));
-        const int gp = (int)std::max<int64_t>(1, std::min<int64_t>(ctx->props.multiProcessorCount,
-                                                                   (specs.shards * specs.n_slots * Gs + 4095) / 4096));
-        hipLaunchKernelGGL(k_fused_plan, dim3(gp), dim3(1024), 0, ctx->stream, mm.as<MinMax>(), nb, pi, g_cap, nd, dim_items,
-                           dplan, st, states.as<uint64_t>(), Gs, specs);
+// pairs: items loaded two per lane (PV); item pairs carry one value column, so two columns load per item
+void launch_slice_probe_dim(qeh_ctx *ctx, const SliceRegions &rg, int nreg, const FastIn &in, const AggSpecs &specs,
+                            int64_t G, uint64_t *states, const DimSlices &dim, int nacol, bool pairs) {
+    const bool pf = slice_probe_prefetch();
+    const int gridB = ctx->props.multiProcessorCount;
+    const HashTable t{};
+#define QEH_SD(NAV, PFV, PVV)                                                                                            \
+    hipLaunchKernelGGL((k_slice_probe<NAV, false, PFV, PVV, true>), dim3(gridB), dim3(kSliceBlock), 0, ctx->stream, rg, \
+                       nreg, 0, t, in, specs, G, states, dim)
+    if (nacol == 0) {
+        if (pf) QEH_SD(0, true, false);
+        else QEH_SD(0, false, false);
+    } else if (nacol == 2) {
+        if (pf) QEH_SD(2, true, false);
+        else QEH_SD(2, false, false);
+    } else if (pairs) {
+        if (pf) QEH_SD(1, true, true);
+        else QEH_SD(1, false, true);
+    } else {
+        if (pf) QEH_SD(1, true, false);
+        else QEH_SD(1, false, false);
     }
-    QEH_HIP(hipGetLastError());
-    FusedPro fp{};
-    fp.dk = (const int64_t *)bk.values + bk.offset;
-    fp.dg = make_colref(gk);
-    fp.nd = nd;
-    fp.ditems = ditems.as<uint32_t>();
-    fp.dcount = dcount.as<uint32_t>();
-    fp.status = st;
-    fp.gkeys = gkeys.p;
-    fp.rep = rep.as<uint32_t>();
-    fp.G = Gs;
-    fp.as32 = gk.dtype == QEH_DT_INT32 ? 1 : 0;
-    fp.plan = dplan;
-    launch_slice_partition_early(ctx, in, pp, nterms, nacol, n_tiles, tail, grid, rg, &dplan->sp, fp);
-    {
-        KernelTimer ktb(ctx, "slice_probe");
-        DimSlices dim{ditems.as<uint32_t>(), dcount.as<uint32_t>(), st + 4, dplan};
-        const bool pf = slice_probe_prefetch();
-        const int gridB = ctx->props.multiProcessorCount;
-        const HashTable t{};
-        // items loaded two per lane (PV, default; QEH_FUSED_PV=0: one per lane)
-        static const bool pv = !(std::getenv("QEH_FUSED_PV") && std::atoi(std::getenv("QEH_FUSED_PV")) == 0);
-#define QEH_SD(NAV, PFV, PVV)                                                                                              \
-    hipLaunchKernelGGL((k_slice_probe<NAV, false, PFV, PVV, true>), dim3(gridB), dim3(kSliceBlock), 0, ctx->stream, rg,   \
-                       grid, 0, t, in, specs, Gs, states.as<uint64_t>(), dim)
-        if (nacol == 0) {
-            if (pf) QEH_SD(0, true, false);
-            else QEH_SD(0, false, false);
-        } else if (nacol == 2) {  // (item pairs carry one value column: two columns load per item)
-            if (pf) QEH_SD(2, true, false);
-            else QEH_SD(2, false, false);
-        } else if (pv) {
-            if (pf) QEH_SD(1, true, true);
-            else QEH_SD(1, false, true);
-        } else {
-            if (pf) QEH_SD(1, true, false);
-            else QEH_SD(1, false, false);
-        }
 #undef QEH_SD
-    }
-    QEH_HIP(hipGetLastError());
-    // fold the shard copies (when there are several), then one workgroup compacts, writes the outputs
-    // and the group count (st[2..3])
-    if (specs.shards > 1) {
-        const int64_t words = (int64_t)specs.n_slots * Gs;
-        hipLaunchKernelGGL(k_states_fold, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, ctx->stream,
-                           states.as<uint64_t>(), Gs, specs);
-    }
-    QEH_HIP(hipGetLastError());
-    qeh_column kc{};
-    kc.dtype = gk.dtype;
-    kc.length = Gs;
-    kc.values = gkeys.p;
-    KeyCols keys{};
-    keys.n = 1;
-    keys.c[0] = make_colref(kc);
-    OutCols oc{};
-    int made = 0;
-    auto cleanup = [&]() {
-        for (int i = 0; i < made; ++i) qeh_column_release(ctx, i == 0 ? &out_keys[0] : &out_aggs[i - 1]);
-        made = 0;
-    };
-    for (int i = 0; i < 1 + specs.n; ++i) {
-        qeh_column *c = i == 0 ? &out_keys[0] : &out_aggs[i - 1];
-        int dt;
-        bool nullable;
-        if (i == 0) {
-            dt = gk.dtype;
-            nullable = false;
-        } else {
-            const AggSpec &sp = specs.a[i - 1];
-            dt = agg_output_type(sp.func, sp.in_type);
-            nullable = sp.func != QEH_AGG_COUNT;
-        }
-        const int s = alloc_column(ctx, dt, Gs, nullable, c);
-        if (s != QEH_OK) {
-            cleanup();
-            return s;
-        }
-        ++made;
-        oc.c[i].values = c->values;
-        oc.c[i].validity = (uint32_t *)c->validity;
-        oc.c[i].dtype = dt;
-    }
-    {
-        KernelTimer kt(ctx, "aggregate_finalize");
-        hipLaunchKernelGGL(k_fused_finish, dim3(1), dim3(1024), 0, ctx->stream, states.as<uint64_t>(), Gs, keys,
-                           rep.as<uint32_t>(), specs, oc, (uint64_t *)(st + 2));
-    }
-    uint32_t sw[8];
-    int s = hipGetLastError() == hipSuccess ? QEH_OK : fail(QEH_E_HIP, "fused join-aggregate: launch failed");
-    if (s == QEH_OK) s = read_small(ctx, sw, errw.p, 32);  // the one host round trip of the query
-    if (s == QEH_OK && !sw[0] && (!sw[5] || sw[1] || sw[4])) s = kFusedNotEligible;  // plan, overflow, duplicates
-    if (s == kFusedNotEligible && !sw[5]) {
-        // the device plan declined: every kernel of this call returned at once, so its timing records
-        // are not a query's phases (the general path that follows records its own)
-        for (size_t i = timing_mark; i < ctx->timing_pending.size(); ++i) ctx->timing_pending[i].name += "_declined";
-    }
-    if (s == QEH_OK) s = kernel_error_status(sw[0], "aggregate");
-    if (s != QEH_OK) {
-        cleanup();
-        return s;
-    }
-    const int64_t out_n = (int64_t)((uint64_t)sw[2] | ((uint64_t)sw[3] << 32));
-    for (int i = 0; i < 1 + specs.n; ++i) {
-        qeh_column *c = i == 0 ? &out_keys[0] : &out_aggs[i - 1];
-        c->length = out_n;
-        c->null_count = c->validity ? -1 : 0;
-    }
-    *out_groups = out_n;
-    return QEH_OK;
 }
+}  // namespace qeh
 
 // ---- the items form of the distributed broadcast join (BASELINE metric at N > 1) ---------------
 // The fused pipeline with the build side sharded over the ranks: every rank groups ITS dimension rows by
@@ -4776,8 +3333,7 @@ static int fused_items_begin(qeh_ctx *ctx, const qeh_column *probe_cols, int n_p
                                                                      (int64_t)kMaxSliceGrid}));
     const uint64_t tiles_per_wg = (uint64_t)((n_all + fi->grid - 1) / fi->grid);
     SlicePlanIn pi{};
-    pi.min_bytes = 6ull << 20;
-    if (const char *e = std::getenv("QEH_SLICE_MIN_BYTES")) pi.min_bytes = std::strtoull(e, nullptr, 10);
+    pi.min_bytes = slice_min_bytes();
     pi.grid = fi->grid;
     pi.n_slots = specs.n_slots;
     pi.sparse_ok = direct_sparse_allowed() ? 1 : 0;

@@ -21,6 +21,7 @@
 #include <string>
 #include <vector>
 
+#include "aggregate.h"
 #include "expr_device.h"
 #include "lookback.h"
 #include "ops.h"

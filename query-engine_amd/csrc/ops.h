@@ -76,12 +76,7 @@ int columns_minmax_collect(qeh_ctx *ctx, const qeh_column *cols, int n, const Mi
 int column_minmax(qeh_ctx *ctx, const qeh_column &col, int64_t *mn, int64_t *mx, int64_t *valid);
 // min / max / valid count of several integer columns, one synchronous read.
 int columns_minmax(qeh_ctx *ctx, const qeh_column *cols, int n, int64_t *mn, int64_t *mx, int64_t *valid);
-// LDS-slice materialising INNER join of one probe payload and one Int64 build
-// payload (k_aggregate.hip); kSliceJoinNotEligible when the shapes do not fit.
-constexpr int kSliceJoinNotEligible = -1;
-int slice_join_materialise(qeh_ctx *ctx, const qeh_column &probe_key, const qeh_column &probe_val,
-                           const qeh_column &build_key, const qeh_column &build_val, qeh_column *out_probe,
-                           qeh_column *out_build, int64_t *out_rows);
+// (the LDS-slice materialising INNER join, slice_join_materialise: aggregate.h)
 int build_join_table(qeh_ctx *ctx, const qeh_column &key, const RowPayload &payload, uint64_t payload_max,
                      BuiltTable *out, int force_kind = -1);
 inline int build_join_table(qeh_ctx *ctx, const qeh_column &key, const uint32_t *row_payload, uint64_t payload_max,
