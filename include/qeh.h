@@ -313,6 +313,19 @@ int qeh_filter_aggregate(qeh_ctx *ctx, const qeh_column *cols, int n_cols, const
                          int64_t input_batches, qeh_column *out_keys, qeh_column *out_aggs,
                          int64_t *out_groups);
 
+/* AVG's last step (operators.rs:770-808): out[i] = (double)sum[i] / (double)count[i] as Float64,
+ * NULL where count[i] is NULL or <= 0 (a group whose inputs were all NULL).  The final stage of a
+ * partial/final plan (distributed/planner.rs:200-226) that carried AVG as SUM and COUNT partials.
+ * sum: Int64 or Float64, count: Int64; either may carry a validity bitmap and a non-zero offset.
+ * A NULL sum reads as 0 (the reference's unwrap_or(0)).
+ * input_dtype: the aggregated column's type (Int32 / Int64 with an Int64 sum, Float32 / Float64 with
+ * a Float64 sum); for QEH_DT_INT32 the Int64 sum is first wrapped to 32 bits and sign-extended,
+ * which is the reference's i32 `compute::sum`.  Any other type is QEH_E_TYPE; a length mismatch or
+ * a null pointer QEH_E_INVALID.  out: an owned Float64 column with a bitmap; out->null_count is
+ * set (one host read). */
+int qeh_avg_finalize(qeh_ctx *ctx, const qeh_column *sum, const qeh_column *count,
+                     int32_t input_dtype, qeh_column *out);
+
 /* Inner equi-join: the intended semantics of executor.rs:363-381 (the
  * reference ignores `on`).  Builds a hash table on
  * `build_key`, probes with `probe_key` (NULL keys never match), and emits the

@@ -95,6 +95,7 @@ SIGNATURES = {
     "qeh_hash_aggregate": (I, [P, COLP, I, COLP, I, AGGP, I, I64, COLP, COLP, C.POINTER(I64)]),
     "qeh_filter_aggregate": (I, [P, COLP, I, EXPRP, C.POINTER(C.c_int32), I, AGGP, I, I64, COLP, COLP,
                                  C.POINTER(I64)]),
+    "qeh_avg_finalize": (I, [P, COLP, COLP, C.c_int32, COLP]),
     "qeh_hash_join_inner": (I, [P, COLP, COLP, I, COLP, COLP, I, COLP, COLP, C.POINTER(I64)]),
     "qeh_hash_join_outer": (I, [P, I, COLP, COLP, I, COLP, COLP, I, COLP, COLP, C.POINTER(I64)]),
     "qeh_hash_join": (I, [P, I, COLP, COLP, I, COLP, COLP, I, COLP, COLP, C.POINTER(I64)]),

@@ -388,6 +388,13 @@ class Context:
             return [], [], 0
         return [self._wrap(ok[i]) for i in range(len(key_idx))], [self._wrap(oa[i]) for i in range(len(aggs))], g.value
 
+    def avg_finalize(self, sum: DeviceColumn, count: DeviceColumn, input_dtype: int) -> DeviceColumn:
+        """qeh_avg_finalize: AVG from its SUM and COUNT columns (Float64, NULL where the count is NULL
+        or <= 0); `input_dtype` is the aggregated column's type (Int32 sums wrap to 32 bits first)."""
+        out = abi.QehColumn()
+        abi.check(self.lib.qeh_avg_finalize(self.h, C.byref(sum.c), C.byref(count.c), int(input_dtype), C.byref(out)))
+        return self._wrap(out)
+
     def copy_d2d(self, dst: int, src: int, nbytes: int) -> None:
         abi.check(self.lib.qeh_memcpy_d2d(self.h, dst, src, nbytes))
 

@@ -12,6 +12,10 @@ stages run for real:
   * hash_join_inner: shuffle both sides by the join key, local device join.
   * group_by: local partial aggregate -> shuffle partial states by the first
     group key -> final aggregate on the owning rank (partial/final stages).
+  * aggregate: the same stages without GROUP BY -- one partial row per rank, all-gathered,
+    final aggregate on rank 0.
+  * AVG in every partial/final plan: carried as SUM + COUNT partials (expand_avg), divided
+    after the final merge on the device (qeh_avg_finalize).
   * row_number: hash shuffle by the partition key, local ROW_NUMBER, reverse
     all-to-all, scatter back into input order.
   * sort: sample splitters, range partition, exchange, stable local sort.
@@ -201,6 +205,40 @@ TYPESTR = {abi.DT_INT64: "<i8", abi.DT_FLOAT64: "<f8", abi.DT_INT32: "<i4", abi.
 
 # partial -> final aggregate decomposition (distributed/planner.rs:200-249 stage shape)
 FINAL_OF = {AF.Count: AF.Sum, AF.Sum: AF.Sum, AF.Min: AF.Min, AF.Max: AF.Max}
+
+# aggregates one fused device operator carries (csrc/agg.h kMaxAggs); qeh_hash_aggregate itself runs
+# longer lists in chunks, so only the join plans are bound by it
+MAX_AGGS_PER_OPERATOR = 8
+
+
+def expand_avg(aggs: Sequence[Tuple[int, int]], max_partials: Optional[int] = MAX_AGGS_PER_OPERATOR):
+    """AVG has no mergeable partial state, so a partial/final plan carries it as SUM and COUNT
+    (planner.rs:200-226 stage shape).  Returns (partial_aggs, recipe):
+      * partial_aggs: `aggs` with every (Avg, c) replaced by (Sum, c) and (Count, c); an identical
+        (Sum, c) / (Count, c) -- one the caller asked for, or another AVG's -- is used instead of a copy;
+      * recipe[i], for requested aggregate i: the int index of its partial column, or for an AVG the
+        tuple (sum index, count index, c), finished by qeh_avg_finalize with column c's dtype.
+    A list without AVG comes back unchanged with the identity recipe.  More than `max_partials`
+    partial aggregates is QEH_E_UNSUPPORTED (None: no bound).  Pure Python: every rank derives the
+    same lists from the same request, before any collective."""
+    aggs = [(f, c) for f, c in aggs]
+    if all(f != AF.Avg for f, _ in aggs):
+        partial, recipe = aggs, list(range(len(aggs)))
+    else:
+        partial, recipe = [], []
+        # what the caller asked for keeps its relative order; an AVG's helpers it did not ask for follow
+        # in place, so every partial column sits where its first user is
+        def slot(fc):
+            if fc not in partial:
+                partial.append(fc)
+            return partial.index(fc)
+        for f, c in aggs:
+            recipe.append((slot((AF.Sum, c)), slot((AF.Count, c)), c) if f == AF.Avg else slot((f, c)))
+    if max_partials is not None and len(partial) > max_partials:
+        raise abi.QehError(abi.QEH_E_UNSUPPORTED,
+                           f"{len(partial)} partial aggregates (AVG counts as SUM + COUNT): one device operator "
+                           f"carries at most {max_partials}")
+    return partial, recipe
 
 
 class DistributedExecutor:
@@ -456,10 +494,13 @@ class DistributedExecutor:
 
     def group_by(self, keys: Sequence[DeviceColumn], inputs: Sequence[DeviceColumn], aggs: Sequence[Tuple[int, int]]):
         """Partial aggregate locally, shuffle partial states by the first key,
-        final aggregate on the owning rank.  Each rank returns the groups it owns."""
-        for f, _ in aggs:
-            if f not in FINAL_OF:
-                raise NotImplementedError("distributed AVG needs SUM+COUNT partials; compose it from them")
+        final aggregate on the owning rank.  Each rank returns the groups it owns.
+        AVG travels as SUM + COUNT partials and is divided after the final merge (expand_avg,
+        _finish_avg).  Results equal qeh_hash_aggregate over the concatenated shards, except that
+        float sums associate differently (per rank, then across ranks)."""
+        partial, recipe = expand_avg(aggs, max_partials=None)  # (qeh_hash_aggregate chunks long lists)
+        if any(f == AF.Avg for f, _ in aggs):
+            return self._finish_avg(self.group_by(keys, inputs, partial), recipe, partial, keys, inputs)
         _refuse_utf8_keys(keys, "group")
         pk, pa_, g = self.ctx.hash_aggregate(keys, inputs, aggs)
         if g == 0:
@@ -478,6 +519,47 @@ class DistributedExecutor:
                 return abi.DT_FLOAT64 if t in (abi.DT_FLOAT64, abi.DT_FLOAT32) else abi.DT_INT64
             return t
         return ([self.ctx.empty(k.dtype, 0) for k in keys], [self.ctx.empty(out_dt(f, c), 0) for f, c in aggs])
+
+    def _finish_avg(self, result, recipe, partial_aggs, keys, inputs):
+        """The step after a plan's final merge when the request held AVG: `result` is the plan's
+        (keys, columns, groups) for expand_avg's partial_aggs.  Every AVG is built from its merged SUM
+        and COUNT by qeh_avg_finalize (the Int32 wrap from the aggregated input's dtype), the helper
+        columns the caller did not ask for are dropped, and the columns come back in the caller's
+        order.  A rank that owns no group returns typed zero-row columns (AVG: Float64)."""
+        fk, fa, g = result
+        if len(fa) != len(partial_aggs):  # no group here: the final aggregate made no columns
+            fk, fa = self._empty_partials(keys, inputs, partial_aggs)
+            g = 0
+        out = []
+        for r in recipe:
+            if isinstance(r, int):
+                out.append(fa[r])
+            else:
+                si, ci, c = r
+                out.append(self.ctx.avg_finalize(fa[si], fa[ci], inputs[c].dtype))
+        return fk, out, g
+
+    def aggregate(self, inputs: Sequence[DeviceColumn], aggs: Sequence[Tuple[int, int]], input_batches: int = 1):
+        """HashAggregate without GROUP BY over rank-sharded rows (executor.rs:157-212 as the
+        partial/final stages of planner.rs:200-226): every rank aggregates its shard into one partial
+        row (none when input_batches == 0), the rows are all-gathered, and the final aggregate runs
+        over them with input_batches = the number of gathered rows, so "no batch anywhere gives no
+        row" survives (executor.rs:178).  AVG as in group_by.  The single result row lives on rank 0
+        (the final stage's single partition); the other ranks return zero-row columns of the same
+        types.  Returns (columns, rows).  One metadata all-gather and one all-gather per column (and
+        per agreed bitmap) on every rank, whatever its shard holds."""
+        partial, recipe = expand_avg(aggs, max_partials=None)
+        _, pa_, g = self.ctx.hash_aggregate([], inputs, partial, input_batches)
+        if g == 0:
+            _, pa_ = self._empty_partials([], inputs, partial)
+        gathered = self.allgather_columns(pa_)
+        rows = len(gathered[0]) if gathered else 0
+        fa, g = [], 0
+        if self.rank == 0:
+            _, fa, g = self.ctx.hash_aggregate([], gathered, [(FINAL_OF[f], i) for i, (f, _) in enumerate(partial)],
+                                               input_batches=rows)
+        _, out, g = self._finish_avg(([], fa, g), recipe, partial, [], inputs)
+        return out, g
 
     def allgather_columns(self, cols: Sequence[DeviceColumn]) -> List[DeviceColumn]:
         """Every rank's shard of `cols`, concatenated in rank order, on every rank: the
@@ -510,7 +592,7 @@ class DistributedExecutor:
         return out
 
     def _gather_padded(self, t: torch.Tensor, n: int, mx: int, rows: Sequence[int]) -> torch.Tensor:
-        if self.world == 1:
+        if self.world == 1 or mx == 0:  # (mx comes from the gathered row counts: the same on every rank)
             return t
         if n < mx:
             pad = torch.zeros(mx, dtype=t.dtype, device=t.device)
@@ -535,10 +617,16 @@ class DistributedExecutor:
         Otherwise `build_*` are replicated already.  Then the fused local pipeline, and the partial
         per-group states are merged on the owning rank (partial/final aggregate,
         distributed/planner.rs:200-249): one dense all-reduce for a bounded integer group key,
-        else a shuffle of the partial states."""
-        for f, _ in aggs:
-            if f not in FINAL_OF:
-                raise NotImplementedError("distributed AVG needs SUM+COUNT partials; compose it from them")
+        else a shuffle of the partial states.
+        AVG travels as SUM + COUNT partials through whichever form runs and is divided after the
+        final merge (expand_avg, _finish_avg): AVG of a non-null Float64 column is a float-SUM lane and
+        a COUNT lane, so it stays on the fast forms.  Results equal the single-device operator over the
+        concatenated shards, except that float sums associate differently."""
+        partial, recipe = expand_avg(aggs)  # raises before any collective: every rank alike
+        if any(f == AF.Avg for f, _ in aggs):
+            out = self.join_filter_aggregate_broadcast(probe_cols, probe_key_idx, predicate, build_key, build_group_keys,
+                                                       partial, build_sharded)
+            return self._finish_avg(out, recipe, partial, build_group_keys, probe_cols)
         # which aggregate inputs may hold NULLs, agreed across ranks (each rank sees only its fact
         # shard's bitmaps; the final stage's choice of collectives must be the same on every rank)
         probe_flags = [1 if probe_cols[c].c.validity else 0 for _, c in aggs]
@@ -1011,10 +1099,13 @@ class DistributedExecutor:
           2. both sides are hash-partitioned by the join key on the device and exchanged with
              one all-to-all per column, so every key's probe and build rows meet on one rank;
           3. the local fused join + aggregate runs on what arrived, and the partial per-group
-             states are shuffled by group key and merged on the owning rank."""
-        for f, _ in aggs:
-            if f not in FINAL_OF:
-                raise NotImplementedError("distributed AVG needs SUM+COUNT partials; compose it from them")
+             states are shuffled by group key and merged on the owning rank.
+        AVG as in join_filter_aggregate_broadcast."""
+        partial, recipe = expand_avg(aggs)  # raises before any collective: every rank alike
+        if any(f == AF.Avg for f, _ in aggs):
+            out = self.join_filter_aggregate_shuffle(probe_cols, probe_key_idx, predicate, build_key, build_group_keys,
+                                                     partial)
+            return self._finish_avg(out, recipe, partial, build_group_keys, probe_cols)
         if self.world == 1:
             # one partition: both hash exchanges and the final merge are the identity, so the plan
             # is the local fused operator on this rank's rows
