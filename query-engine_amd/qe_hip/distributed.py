@@ -241,6 +241,55 @@ def expand_avg(aggs: Sequence[Tuple[int, int]], max_partials: Optional[int] = MA
     return partial, recipe
 
 
+def _lane_dtypes(aggs: Sequence[Tuple[int, int]]) -> List[int]:
+    """Column types of the dense final stage's COUNT / float-SUM lanes."""
+    return [abi.DT_INT64 if f == AF.Count else abi.DT_FLOAT64 for f, _ in aggs]
+
+
+def _dense_join_schema(build_key, build_group_keys, aggs=()) -> bool:
+    """The schema-level test of the device broadcast forms and both items forms (identical on every
+    rank): one integer group key, an Int64 join key, COUNT / SUM only where `aggs` is given."""
+    return (len(build_group_keys) == 1 and build_key.dtype == abi.DT_INT64
+            and build_group_keys[0].dtype in (abi.DT_INT64, abi.DT_INT32)
+            and all(f in (AF.Count, AF.Sum) for f, _ in aggs))
+
+
+def items_plan(M: np.ndarray, aggs: Sequence[Tuple[int, int]], slices: int, state_words: int,
+               min_table_bytes: int) -> Optional[Tuple[int, int, int]]:
+    """Whether an items form runs, from the gathered 7-word stats rows M[world] = [rows, key min, max,
+    group key min, max, has-bitmap, shape ok] alone, so every rank decides alike: every rank's shape
+    fits, no bitmap, some dimension row, at most `slices` 2^16-key slices, the group states within
+    `state_words`, and a key range whose u16 table would reach `min_table_bytes`.  Returns
+    (group key min, groups, the largest shard's rows) or None."""
+    live = M[M[:, 0] > 0]
+    if not (M[:, 6].min() == 1 and M[:, 5].max() == 0 and len(live)):
+        return None
+    R = int(live[:, 2].max()) - int(live[:, 1].min()) + 1
+    gmin = int(live[:, 3].min())
+    G = int(live[:, 4].max()) - gmin + 1
+    F = (R + (1 << 16) - 1) >> 16
+    n_sum = sum(1 for f, _ in aggs if f == AF.Sum)
+    if not (1 <= F <= slices and G * (1 + n_sum) <= state_words and 2 * R >= min_table_bytes):
+        return None
+    return gmin, G, int(M[:, 0].max())
+
+
+def _pad_rows(t: torch.Tensor, mx: int) -> torch.Tensor:
+    """`t` zero-padded to mx rows, contiguous: a shard as a padded all-gather sends it."""
+    if t.shape[0] < mx:
+        pad = torch.zeros(mx, dtype=t.dtype, device=t.device)
+        pad[:t.shape[0]] = t
+        t = pad
+    return t.contiguous()
+
+
+def _trim_rows(buf: torch.Tensor, rows: Sequence[int], mx: int) -> torch.Tensor:
+    """A padded all-gather's [len(rows) x mx] result without the padding of the ragged shards."""
+    if all(r == mx for r in rows):
+        return buf
+    return torch.cat([buf[q * mx:q * mx + r] for q, r in enumerate(rows)])
+
+
 class DistributedExecutor:
     def __init__(self, ctx: Context, group=None, device: Optional[str] = None):
         """device: where payloads live during collectives — "cuda" under "nccl" (RCCL), "cpu" under
@@ -253,6 +302,7 @@ class DistributedExecutor:
         self.world = dist.get_world_size(group)
         self.device = device or ("cuda" if dist.get_backend(group) == "nccl" else "cpu")
         self.last_final = None  # how the last broadcast join merged its partial states
+        self._pinned = {}  # pinned host buffers of the stats rows by row length, reused every step
 
     # ---- column <-> tensor ------------------------------------------------------
     def _bits_to_bytes(self, col: DeviceColumn, bits_ptr: int) -> torch.Tensor:
@@ -326,11 +376,8 @@ class DistributedExecutor:
             keep = [vals]
             bitmap = 0
             if valid is not None:
-                bm = torch.zeros(((n + 63) // 64) * 8 + 8, dtype=torch.uint8, device="cuda")
-                if n:
-                    abi.check(self.ctx.lib.qeh_bytes_to_validity(self.ctx.h, valid.data_ptr(), n, bm.data_ptr()))
-                keep.append(bm)
-                bitmap = bm.data_ptr()
+                keep.append(self._bytes_to_bits(valid))
+                bitmap = keep[-1].data_ptr()
             if n == 0:  # a non-null pointer for empty columns
                 keep[0] = torch.empty(1, dtype=vals.dtype, device="cuda")
             d = self.ctx.wrap_device(dtype, keep[0].data_ptr(), n, bitmap)
@@ -498,14 +545,27 @@ class DistributedExecutor:
         AVG travels as SUM + COUNT partials and is divided after the final merge (expand_avg,
         _finish_avg).  Results equal qeh_hash_aggregate over the concatenated shards, except that
         float sums associate differently (per rank, then across ranks)."""
-        partial, recipe = expand_avg(aggs, max_partials=None)  # (qeh_hash_aggregate chunks long lists)
+        def plan(aggs):
+            _refuse_utf8_keys(keys, "group")
+            pk, pa_ = self._partials_or_empty(self.ctx.hash_aggregate(keys, inputs, aggs), keys, inputs, aggs)
+            return self._final(pk, pa_, aggs)
+        return self._with_avg(plan, aggs, keys, inputs, max_partials=None)  # (qeh_hash_aggregate chunks long lists)
+
+    def _with_avg(self, plan, aggs, keys, inputs, max_partials=MAX_AGGS_PER_OPERATOR):
+        """A partial/final plan with AVG in the request: `plan` runs over expand_avg's partial list (the
+        request itself when it holds no AVG), and _finish_avg divides after the final merge.  expand_avg
+        raises before any collective, on every rank alike."""
+        partial, recipe = expand_avg(aggs, max_partials)
+        out = plan(partial)
         if any(f == AF.Avg for f, _ in aggs):
-            return self._finish_avg(self.group_by(keys, inputs, partial), recipe, partial, keys, inputs)
-        _refuse_utf8_keys(keys, "group")
-        pk, pa_, g = self.ctx.hash_aggregate(keys, inputs, aggs)
-        if g == 0:
-            pk, pa_ = self._empty_partials(keys, inputs, aggs)
-        return self._final(pk, pa_, aggs)
+            out = self._finish_avg(out, recipe, partial, keys, inputs)
+        return out
+
+    def _partials_or_empty(self, result, keys, inputs, aggs):
+        """(keys, partial states) of a local aggregate's (keys, states, groups); typed zero-row columns
+        when this rank has no group (the operator made no columns then)."""
+        pk, pa_, g = result
+        return (pk, pa_) if g else self._empty_partials(keys, inputs, aggs)
 
     def _empty_partials(self, keys, inputs, aggs):
         """Zero-row partial states with the types every other rank's partials have (SUM of a
@@ -549,9 +609,7 @@ class DistributedExecutor:
         types.  Returns (columns, rows).  One metadata all-gather and one all-gather per column (and
         per agreed bitmap) on every rank, whatever its shard holds."""
         partial, recipe = expand_avg(aggs, max_partials=None)
-        _, pa_, g = self.ctx.hash_aggregate([], inputs, partial, input_batches)
-        if g == 0:
-            _, pa_ = self._empty_partials([], inputs, partial)
+        _, pa_ = self._partials_or_empty(self.ctx.hash_aggregate([], inputs, partial, input_batches), [], inputs, partial)
         gathered = self.allgather_columns(pa_)
         rows = len(gathered[0]) if gathered else 0
         fa, g = [], 0
@@ -582,27 +640,21 @@ class DistributedExecutor:
         self._sync()  # the views / validity bytes are produced on the library's queue
         for j, c in enumerate(cols):
             ts = tens[j]
-            vals = self._gather_padded(ts[0], n, mx, rows)
+            vals = self._gather_padded(ts[0], mx, rows)
             valid = None
             if nullable[j]:
                 vb = ts[1] if len(ts) > 1 else torch.ones(n, dtype=torch.uint8, device=self.device)
-                valid = self._gather_padded(vb, n, mx, rows)
+                valid = self._gather_padded(vb, mx, rows)
             out.append(self._from_tensors(c.dtype, vals, valid))
         self._sync_torch()
         return out
 
-    def _gather_padded(self, t: torch.Tensor, n: int, mx: int, rows: Sequence[int]) -> torch.Tensor:
+    def _gather_padded(self, t: torch.Tensor, mx: int, rows: Sequence[int]) -> torch.Tensor:
         if self.world == 1 or mx == 0:  # (mx comes from the gathered row counts: the same on every rank)
             return t
-        if n < mx:
-            pad = torch.zeros(mx, dtype=t.dtype, device=t.device)
-            pad[:n] = t
-            t = pad
         buf = torch.empty(self.world * mx, dtype=t.dtype, device=t.device)
-        dist.all_gather_into_tensor(buf, t.contiguous(), group=self.group)
-        if all(r == mx for r in rows):
-            return buf
-        return torch.cat([buf[q * mx:q * mx + rows[q]] for q in range(self.world)])
+        dist.all_gather_into_tensor(buf, _pad_rows(t, mx), group=self.group)
+        return _trim_rows(buf, rows, mx)
 
     def join_filter_aggregate_broadcast(self, probe_cols, probe_key_idx, predicate, build_key, build_group_keys,
                                         aggs, build_sharded: bool = False):
@@ -622,11 +674,12 @@ class DistributedExecutor:
         final merge (expand_avg, _finish_avg): AVG of a non-null Float64 column is a float-SUM lane and
         a COUNT lane, so it stays on the fast forms.  Results equal the single-device operator over the
         concatenated shards, except that float sums associate differently."""
-        partial, recipe = expand_avg(aggs)  # raises before any collective: every rank alike
-        if any(f == AF.Avg for f, _ in aggs):
-            out = self.join_filter_aggregate_broadcast(probe_cols, probe_key_idx, predicate, build_key, build_group_keys,
-                                                       partial, build_sharded)
-            return self._finish_avg(out, recipe, partial, build_group_keys, probe_cols)
+        return self._with_avg(lambda a: self._broadcast_join(probe_cols, probe_key_idx, predicate, build_key,
+                                                             build_group_keys, a, build_sharded),
+                              aggs, build_group_keys, probe_cols)
+
+    def _broadcast_join(self, probe_cols, probe_key_idx, predicate, build_key, build_group_keys, aggs, build_sharded):
+        """join_filter_aggregate_broadcast over a request without AVG."""
         # which aggregate inputs may hold NULLs, agreed across ranks (each rank sees only its fact
         # shard's bitmaps; the final stage's choice of collectives must be the same on every rank)
         probe_flags = [1 if probe_cols[c].c.validity else 0 for _, c in aggs]
@@ -656,10 +709,9 @@ class DistributedExecutor:
             build_key, build_group_keys = full[0], full[1:]
         if probe_nullable is None:
             probe_nullable = self._agree_max(probe_flags)
-        pk, pa_, g = self.ctx.join_filter_aggregate(probe_cols, probe_key_idx, predicate, build_key,
-                                                    build_group_keys, aggs)
-        if g == 0:
-            pk, pa_ = self._empty_partials(build_group_keys, probe_cols, aggs)
+        pk, pa_ = self._partials_or_empty(
+            self.ctx.join_filter_aggregate(probe_cols, probe_key_idx, predicate, build_key, build_group_keys, aggs),
+            build_group_keys, probe_cols, aggs)
         gcol = build_group_keys[0] if len(build_group_keys) == 1 else None
         dense = None
         if gcol is not None and gcol.dtype in (abi.DT_INT64, abi.DT_INT32) and not gcol.c.validity and len(gcol):
@@ -681,6 +733,35 @@ class DistributedExecutor:
         dist.all_reduce(t, op=dist.ReduceOp.MAX, group=self.group)
         return t.cpu().numpy()
 
+    def _gather_stats(self, build_key, group_key, extra: Sequence[int]):
+        """The stats-row protocol of every device join form: this dimension shard's [rows, key min / max,
+        group key min / max, *extra] written on the device by one library call (min / max kernels, no
+        host wait), gathered over the ranks, and its copy to the host queued.  Returns (the gathered
+        device rows, a callable that waits for the copy and gives the [world, 5 + len(extra)] host
+        matrix).  The caller queues phase A between the two: a copy queued behind phase A would wait
+        for its workgroups to leave the CUs (the copy engine's blit kernel needs a CU), so the host
+        would sit idle for the whole of phase A before it could queue the build and phase B."""
+        row = torch.empty(5 + len(extra), dtype=torch.int64, device="cuda")
+        self._sync_torch()
+        self.ctx.broadcast_stats(build_key, group_key, extra, row.data_ptr())
+        self._sync()
+        if self.world > 1:
+            out = torch.empty(self.world * row.numel(), dtype=torch.int64, device="cuda")
+            dist.all_gather_into_tensor(out, row, group=self.group)
+            row = out
+        # (one pinned buffer per row length, reused every step: the matrix is copied out of it)
+        pinned = self._pinned.get(row.numel())
+        if pinned is None:
+            pinned = self._pinned[row.numel()] = torch.empty(row.numel(), dtype=torch.int64, pin_memory=True)
+        pinned.copy_(row, non_blocking=True)
+        copied = torch.cuda.Event()
+        copied.record()
+
+        def host_rows():
+            copied.synchronize()
+            return pinned.numpy().reshape(self.world, -1).copy()
+        return row, host_rows
+
     def _build_stats(self, build_key, build_group_keys, probe_flags: Sequence[int], probe=None):
         """One small all_gather of every dimension shard's [rows, key min / max, group key min / max,
         has-bitmap] and the fact shard's aggregate-input bitmap flags: the job-wide ranges both
@@ -688,32 +769,11 @@ class DistributedExecutor:
         schema-level facts, identical on every rank).  Every later branch depends only on gathered
         values, so all ranks take the same one."""
         cols = [build_key] + list(build_group_keys)
-        if (self.device != "cuda" or len(build_group_keys) != 1 or build_key.dtype != abi.DT_INT64
-                or build_group_keys[0].dtype not in (abi.DT_INT64, abi.DT_INT32)):
+        if self.device != "cuda" or not _dense_join_schema(build_key, build_group_keys):
             return None
         n = len(build_key)
         flags = [1 if any(c.c.validity for c in cols) else 0] + list(probe_flags)
-        # [rows, key min / max, group key min / max, flags] written on the device by one library call
-        # (min / max kernels, no host wait), gathered over the ranks, read back once
-        row = torch.empty(5 + len(flags), dtype=torch.int64, device="cuda")
-        self._sync_torch()
-        self.ctx.broadcast_stats(build_key, build_group_keys[0], flags, row.data_ptr())
-        self._sync()
-        if self.world > 1:
-            out = torch.empty(self.world * row.numel(), dtype=torch.int64, device="cuda")
-            dist.all_gather_into_tensor(out, row, group=self.group)
-            row = out
-        # the rows' copy to the host is queued ahead of phase A: a copy queued behind it would wait for
-        # phase A's workgroups to leave the CUs (the copy engine's blit kernel needs a CU), so the host
-        # would sit idle for the whole of phase A before it could queue the build and phase B
-        # (one pinned buffer per row size, reused every step: M below is copied out of it)
-        pinned = getattr(self, "_stats_pinned", None)
-        if pinned is None or pinned.numel() != row.numel():
-            pinned = self._stats_pinned = torch.empty(row.numel(), dtype=torch.int64, pin_memory=True)
-        row_host = pinned
-        row_host.copy_(row, non_blocking=True)
-        copied = torch.cuda.Event()
-        copied.record()
+        row, host_rows = self._gather_stats(build_key, build_group_keys[0], flags)
         prelaunched = False
         # the table form's u16 table of the previous step, zeroed here -- ahead of phase A on the queue --
         # for this step to reuse when its key range is the same: zeroed behind phase A it waited for
@@ -728,8 +788,7 @@ class DistributedExecutor:
             self._sync_torch()
             self.ctx.join_filter_aggregate_prelaunch_stats(*probe, row.data_ptr(), self.world, 5 + len(flags))
             prelaunched = True
-        copied.synchronize()
-        M = row_host.numpy().reshape(self.world, -1).copy()
+        M = host_rows()
         rows = [int(x) for x in M[:, 0]]
         total = sum(rows)
         out = {"M": M, "rows": rows, "total": total, "n": n, "cols": cols, "bitmap": bool(M[:, 5].max() > 0),
@@ -757,69 +816,28 @@ class DistributedExecutor:
         device declines, a region overflow or a key on two ranks come back in the status lane of the
         lanes' all-reduce, and every rank then returns None (the caller takes the table / all-gather
         form).  Returns the dense final ([keys], aggs, groups) or None."""
-        if (self.device != "cuda" or len(build_group_keys) != 1 or build_key.dtype != abi.DT_INT64
-                or build_group_keys[0].dtype not in (abi.DT_INT64, abi.DT_INT32)
-                or any(f not in (AF.Count, AF.Sum) for f, _ in aggs)):
+        if self.device != "cuda" or not _dense_join_schema(build_key, build_group_keys, aggs):
             return None
         gkc = build_group_keys[0]
-        local_ok = 1 if self.ctx.fused_items_check(probe_cols, probe_key_idx, predicate, aggs) else 0
-        bitmap = 1 if (build_key.c.validity or gkc.c.validity) else 0
-        row_len = 7  # [rows, key min, max, group key min, max, has-bitmap, shape ok]
-        row = torch.empty(row_len, dtype=torch.int64, device="cuda")
-        self._sync_torch()
-        self.ctx.broadcast_stats(build_key, gkc, [bitmap, local_ok], row.data_ptr())
-        self._sync()
-        if self.world > 1:
-            out = torch.empty(self.world * row_len, dtype=torch.int64, device="cuda")
-            dist.all_gather_into_tensor(out, row, group=self.group)
-            row = out
-        pinned = getattr(self, "_items_pinned", None)
-        if pinned is None or pinned.numel() != row.numel():
-            pinned = self._items_pinned = torch.empty(row.numel(), dtype=torch.int64, pin_memory=True)
-        pinned.copy_(row, non_blocking=True)  # queued ahead of phase A (a copy behind it would wait for it)
-        copied = torch.cuda.Event()
-        copied.record()
-        handle = None
-        if local_ok:  # phase A planned on the device from the gathered rows, while the host reads them
-            self._sync_torch()
-            try:
-                handle = self.ctx.fused_items_begin(probe_cols, probe_key_idx, predicate, aggs, row.data_ptr(),
-                                                    self.world, row_len)
-            except abi.QehError:
-                handle = None  # (an OOM on this rank: it still joins every collective below, see `failed`)
-        copied.synchronize()
-        M = pinned.numpy().reshape(self.world, row_len).copy()
-        live = M[M[:, 0] > 0]
-        total = int(M[:, 0].sum())
-        n_sum = sum(1 for f, _ in aggs if f == AF.Sum)
-        ok = bool(M[:, 6].min() == 1 and M[:, 5].max() == 0 and total > 0)
-        if ok:
-            kmin, kmax = int(live[:, 1].min()), int(live[:, 2].max())
-            gmin, gmax = int(live[:, 3].min()), int(live[:, 4].max())
-            R, G = kmax - kmin + 1, gmax - gmin + 1
-            F = (R + (1 << 16) - 1) >> 16
-            ok = (1 <= F <= self.ITEMS_SLICES and G * (1 + n_sum) <= self.ITEMS_STATE_WORDS
-                  and 2 * R >= self.ITEMS_MIN_TABLE_BYTES)
-        if not ok:
-            if handle is not None:
-                self.ctx.fused_items_abort(handle)
+        opened = self._items_open(
+            lambda stats, row_len: self.ctx.fused_items_begin(probe_cols, probe_key_idx, predicate, aggs, stats,
+                                                              self.world, row_len),
+            probe_cols, probe_key_idx, predicate, build_key, gkc, aggs)
+        if opened is None:
             return None
+        handle, gmin, G, nb, span = opened
         # this rank's build rows grouped by slice (spans of ~8 K rows, one run per slice each), all-gathered:
         # 4 B per dimension row (+ the runs' padding to 16 B); every rank uses the same shape
-        nb, span = self.ctx.fused_items_shape(int(M[:, 0].max()), self.world)
         OW = 2 * (self.ITEMS_SLICES + 1)
-        # A library error on this rank only (begin / build / finish: e.g. out of memory) must not leave the
-        # other ranks waiting in a collective: this rank sends empty items and a set status lane, so every
-        # rank's lanes come back flagged and every rank returns None together.
-        failed = handle is None
         items = torch.zeros(nb * span, dtype=torch.int32, device="cuda")
         offs = torch.zeros(nb * OW, dtype=torch.int32, device="cuda")
         self._sync_torch()
-        if not failed:
+        if handle is not None:
             try:
                 self.ctx.fused_items_build(handle, build_key, gkc, nb, span, items.data_ptr(), offs.data_ptr())
-            except abi.QehError:
-                failed = True
+            except abi.QehError:  # this rank sends empty items and, in _items_finish, a set status lane
+                self.ctx.fused_items_abort(handle)
+                handle = None
                 items.zero_(), offs.zero_()
         self._sync()
         if self.world > 1:
@@ -828,32 +846,74 @@ class DistributedExecutor:
             dist.all_gather_into_tensor(gi, items, group=self.group)
             dist.all_gather_into_tensor(go, offs, group=self.group)
             items, offs = gi, go
+        return self._items_finish(
+            handle, lambda h, lanes: self.ctx.fused_items_finish(h, items.data_ptr(), span, offs.data_ptr(),
+                                                                 self.world * nb, G, lanes),
+            aggs, gmin, G, gkc.dtype)
+
+    def _items_open(self, begin, probe_cols, probe_key_idx, predicate, build_key, gkc, aggs):
+        """The opening both items forms share: this rank's shape check travels in its 7-word stats row
+        [rows, key min, max, group key min, max, has-bitmap, shape ok]; phase A (`begin(gathered rows'
+        pointer, row length)` -> handle) is planned on the device from the gathered rows and queued while
+        the host reads them; items_plan then decides from the gathered rows alone.  Returns None when
+        every rank declines (a handle is aborted), else (handle, group key min, groups, n_blocks, span)
+        with the build's shape for the largest shard, the same on every rank.  handle None: begin failed
+        on this rank only (e.g. out of memory) -- it still joins every collective of the form, see
+        _items_finish."""
+        local_ok = 1 if self.ctx.fused_items_check(probe_cols, probe_key_idx, predicate, aggs) else 0
+        bitmap = 1 if (build_key.c.validity or gkc.c.validity) else 0
+        row, host_rows = self._gather_stats(build_key, gkc, [bitmap, local_ok])
+        handle = None
+        if local_ok:
+            self._sync_torch()
+            try:
+                handle = begin(row.data_ptr(), 7)
+            except abi.QehError:
+                handle = None
+        plan = items_plan(host_rows(), aggs, self.ITEMS_SLICES, self.ITEMS_STATE_WORDS, self.ITEMS_MIN_TABLE_BYTES)
+        if plan is None:
+            if handle is not None:
+                self.ctx.fused_items_abort(handle)
+            return None
+        gmin, G, max_rows = plan
+        return (handle, gmin, G) + self.ctx.fused_items_shape(max_rows, self.world)
+
+    def _items_finish(self, handle, finish, aggs, gmin: int, G: int, gdtype: int):
+        """The end both items forms share: phase B (`finish(handle, lanes pointer)`; it frees the handle,
+        also when it fails) writes the dense final stage's lanes, then their all-reduce and the take.
+        A rank whose library call failed -- here, or earlier (handle None: aborted already) -- sends
+        zeroed lanes with the status lane set, so every rank's lanes come back flagged and every rank
+        returns None together (the caller takes its next form) instead of waiting in a collective.
+        A plan the device declined, a region overflow or a key on two ranks arrive in the same lane."""
         nl = (1 + len(aggs)) * G + 1  # + the status lane
         lanes = torch.empty(nl, dtype=torch.float64, device="cuda")
         self._sync_torch()
+        failed = handle is None
         if not failed:
             try:
-                self.ctx.fused_items_finish(handle, items.data_ptr(), span, offs.data_ptr(), self.world * nb, G,
-                                            lanes.data_ptr())
+                finish(handle, lanes.data_ptr())
             except abi.QehError:
                 failed = True
-            handle = None  # (finish frees it, also when it fails)
         if failed:
-            if handle is not None:
-                self.ctx.fused_items_abort(handle)
             lanes.zero_()
             lanes[nl - 1] = 1.0
+        got, ov, g, bad = self._merge_lanes(lanes, _lane_dtypes(aggs), gmin, G, gdtype, status=True)
+        if bad != 0.0:
+            return None
+        self.last_final = "dense"
+        return [got], ov, g
+
+    def _merge_lanes(self, lanes: torch.Tensor, out_dtypes: Sequence[int], key_min: int, key_range: int,
+                     key_dtype: int, status: bool = False):
+        """The dense final stage's merge: the ranks' f64 lanes [1 + values][key_range] (+ a status lane
+        with `status`) summed by one all-reduce, and this rank's groups taken out of the sum:
+        (keys, value columns, groups), with `status` also the summed status lane."""
         self._sync()
         if self.world > 1:
             dist.all_reduce(lanes, op=dist.ReduceOp.SUM, group=self.group)
         self._sync_torch()
-        got, ov, g, bad = self.ctx.dense_states_take_status(
-            lanes.data_ptr(), len(aggs), gmin, G, self.world, self.rank, gkc.dtype,
-            [abi.DT_INT64 if f == AF.Count else abi.DT_FLOAT64 for f, _ in aggs])
-        if bad != 0.0:  # declined, overflowed or a repeated key on some rank (the same lane on every rank)
-            return None
-        self.last_final = "dense"
-        return [got], ov, g
+        take = self.ctx.dense_states_take_status if status else self.ctx.dense_states_take
+        return take(lanes.data_ptr(), len(out_dtypes), key_min, key_range, self.world, self.rank, key_dtype, out_dtypes)
 
     def _broadcast_table(self, st, probe_cols, probe_key_idx, predicate, build_key, build_group_keys, aggs,
                          probe_nullable):
@@ -903,6 +963,15 @@ class DistributedExecutor:
         if self.world > 1:
             dist.all_reduce(table, op=dist.ReduceOp.SUM, group=self.group)  # u16 pairs: no carries (checked above)
         self._sync_torch()
+
+        def lanes_inline():
+            # the fused operator, its checks inline, writes the dense final stage's lanes itself (row counts,
+            # COUNT / float SUM partials per group slot): no compaction, output columns or re-scatter
+            lanes = torch.empty((1 + len(aggs)) * G, dtype=torch.float64, device="cuda")
+            self._sync_torch()
+            self.ctx.join_filter_aggregate_table_lanes(probe_cols, probe_key_idx, predicate, table.data_ptr(), kmin, R,
+                                                       G, aggs, lanes.data_ptr())
+            return self._merge_lanes(lanes, _lane_dtypes(aggs), gmin, G, st["gdtype"])
         if no_wait:
             # no host wait until the final states: the duplicate check (non-empty entries of the summed
             # table, the same on every rank) and the operator's status words (error bits, a slice region
@@ -921,13 +990,7 @@ class DistributedExecutor:
             self.ctx.u16_table_check_dev(table.data_ptr(), R, G, lanes_buf[nl:].data_ptr())
             self.ctx.join_filter_aggregate_table_lanes_async(probe_cols, probe_key_idx, predicate, table.data_ptr(), kmin,
                                                              R, G, aggs, lanes.data_ptr(), status.data_ptr())
-            self._sync()
-            if self.world > 1:
-                dist.all_reduce(lanes, op=dist.ReduceOp.SUM, group=self.group)
-            self._sync_torch()
-            ok, ov, g = self.ctx.dense_states_take(lanes.data_ptr(), len(aggs), gmin, G, self.world, self.rank,
-                                                   st["gdtype"],
-                                                   [abi.DT_INT64 if f == AF.Count else abi.DT_FLOAT64 for f, _ in aggs])
+            ok, ov, g = self._merge_lanes(lanes, _lane_dtypes(aggs), gmin, G, st["gdtype"])
             tail = lanes_buf[nl - 1:].cpu().numpy()  # [status lane, non-empty count]
             nz, bad = int(tail[1:].view(np.int64)[0]), float(tail[0]) != 0.0
             self.last_table_redo = False
@@ -935,41 +998,18 @@ class DistributedExecutor:
                 return None  # a build key repeats: the general path handles multi-match joins
             if bad:  # some rank's operator overflowed a slice region (or failed): redo it with the checks inline
                 self.last_table_redo = True
-                lanes = torch.empty((1 + len(aggs)) * G, dtype=torch.float64, device="cuda")
-                self._sync_torch()
-                self.ctx.join_filter_aggregate_table_lanes(probe_cols, probe_key_idx, predicate, table.data_ptr(),
-                                                           kmin, R, G, aggs, lanes.data_ptr())
-                self._sync()
-                if self.world > 1:
-                    dist.all_reduce(lanes, op=dist.ReduceOp.SUM, group=self.group)
-                self._sync_torch()
-                ok, ov, g = self.ctx.dense_states_take(lanes.data_ptr(), len(aggs), gmin, G, self.world, self.rank,
-                                                       st["gdtype"],
-                                                       [abi.DT_INT64 if f == AF.Count else abi.DT_FLOAT64 for f, _ in aggs])
+                ok, ov, g = lanes_inline()
             self.last_final = "dense"
             return [ok], ov, g
         if self.ctx.u16_count_nonzero(table.data_ptr(), R) != total:
             return None  # a build key repeats: the general path handles multi-match joins
         if lanes_ok:
-            # the fused operator writes the dense final stage's lanes itself (row counts, COUNT / float
-            # SUM partials per group slot): no compaction, output columns or re-scatter of the partials
-            lanes = torch.empty((1 + len(aggs)) * G, dtype=torch.float64, device="cuda")
-            self._sync_torch()
-            self.ctx.join_filter_aggregate_table_lanes(probe_cols, probe_key_idx, predicate, table.data_ptr(), kmin, R,
-                                                       G, aggs, lanes.data_ptr())
-            self._sync()
-            if self.world > 1:
-                dist.all_reduce(lanes, op=dist.ReduceOp.SUM, group=self.group)
-            self._sync_torch()
-            ok, ov, g = self.ctx.dense_states_take(lanes.data_ptr(), len(aggs), gmin, G, self.world, self.rank,
-                                                   st["gdtype"],
-                                                   [abi.DT_INT64 if f == AF.Count else abi.DT_FLOAT64 for f, _ in aggs])
+            ok, ov, g = lanes_inline()
             self.last_final = "dense"
             return [ok], ov, g
-        pk, pa_, g = self.ctx.join_filter_aggregate_table(probe_cols, probe_key_idx, predicate, table.data_ptr(), kmin,
-                                                          R, gmin, G, st["gdtype"], aggs)
-        if g == 0:
-            pk, pa_ = self._empty_partials(build_group_keys, probe_cols, aggs)
+        pk, pa_ = self._partials_or_empty(
+            self.ctx.join_filter_aggregate_table(probe_cols, probe_key_idx, predicate, table.data_ptr(), kmin, R, gmin,
+                                                 G, st["gdtype"], aggs), build_group_keys, probe_cols, aggs)
         dense = self._final_dense(gmin, gmax, probe_nullable, pk, pa_, aggs)
         self.last_final = "dense" if dense is not None else "shuffle"
         return dense if dense is not None else self._final(pk, pa_, aggs)
@@ -982,29 +1022,21 @@ class DistributedExecutor:
         caller all-gathers first)."""
         if self.world == 1 or st["bitmap"] or not st["total"]:
             return None
-        rows, n = st["rows"], st["n"]
+        rows = st["rows"]
         ts = [self._to_tensors(c)[0] for c in st["cols"]]
         mx = max(rows)
         bufs, works = [], []
         for t in ts:
-            if n < mx:
-                pad = torch.zeros(mx, dtype=t.dtype, device=t.device)
-                pad[:n] = t
-                t = pad
             buf = torch.empty(self.world * mx, dtype=t.dtype, device=t.device)
-            works.append(dist.all_gather_into_tensor(buf, t.contiguous(), group=self.group, async_op=True))
+            works.append(dist.all_gather_into_tensor(buf, _pad_rows(t, mx), group=self.group, async_op=True))
             bufs.append(buf)
         if not st["prelaunched"]:
             self.ctx.join_filter_aggregate_prelaunch(probe_cols, probe_key_idx, predicate, aggs, st["krange"],
                                                      st["grange"])
         for w in works:
             w.wait()
-        out = []
-        dts = [abi.DT_INT64, st["gdtype"]]
-        for dt, buf in zip(dts, bufs):
-            if any(r != mx for r in rows):
-                buf = torch.cat([buf[q * mx:q * mx + rows[q]] for q in range(self.world)])
-            out.append(self._from_tensors(dt, buf, None))
+        out = [self._from_tensors(dt, _trim_rows(buf, rows, mx), None)
+               for dt, buf in zip([abi.DT_INT64, st["gdtype"]], bufs)]
         self._sync_torch()
         return out
 
@@ -1044,12 +1076,7 @@ class DistributedExecutor:
             self._sync_torch()
             # (SUM partials carry a bitmap but no NULL: every input is non-null, checked above)
             self.ctx.dense_states_f64(pk[0], [_without_bitmap(self.ctx, c) for c in pa_], lo, R, lanes.data_ptr())
-            self._sync()
-            if self.world > 1:
-                dist.all_reduce(lanes, op=dist.ReduceOp.SUM, group=self.group)
-            self._sync_torch()
-            ok, ov, g = self.ctx.dense_states_take(lanes.data_ptr(), len(pa_), lo, R, self.world, self.rank, pk[0].dtype,
-                                                   [c.dtype for c in pa_])
+            ok, ov, g = self._merge_lanes(lanes, [c.dtype for c in pa_], lo, R, pk[0].dtype)
             return [ok], ov, g
         self._sync()
         gk = self._to_tensors(pk[0])[0]
@@ -1063,7 +1090,7 @@ class DistributedExecutor:
         fbuf[0].index_fill_(0, idx, 1.0)
         for q, j in enumerate(fl[1:], 1):
             fbuf[q].index_copy_(0, idx, vals[j].to(torch.float64))
-        dist.all_reduce(fbuf, op=dist.ReduceOp.SUM, group=self.group)
+        merges = [(fbuf, dist.ReduceOp.SUM)]
         ibufs = {}
         for op, js in il.items():
             if not js:
@@ -1072,9 +1099,10 @@ class DistributedExecutor:
             b = torch.full((len(js), R), init, dtype=torch.int64, device=dev)
             for q, j in enumerate(js):
                 b[q].index_copy_(0, idx, vals[j].to(torch.int64))
-            rop = {AF.Sum: dist.ReduceOp.SUM, AF.Min: dist.ReduceOp.MIN, AF.Max: dist.ReduceOp.MAX}[op]
-            dist.all_reduce(b, op=rop, group=self.group)
+            merges.append((b, {AF.Sum: dist.ReduceOp.SUM, AF.Min: dist.ReduceOp.MIN, AF.Max: dist.ReduceOp.MAX}[op]))
             ibufs[op] = (js, b)
+        for b, rop in merges:
+            dist.all_reduce(b, op=rop, group=self.group)
         keys = torch.arange(R, device=dev)
         own = (fbuf[0] > 0) & (keys % self.world == self.rank)
         sel = torch.nonzero(own).flatten()
@@ -1101,18 +1129,18 @@ class DistributedExecutor:
           3. the local fused join + aggregate runs on what arrived, and the partial per-group
              states are shuffled by group key and merged on the owning rank.
         AVG as in join_filter_aggregate_broadcast."""
-        partial, recipe = expand_avg(aggs)  # raises before any collective: every rank alike
-        if any(f == AF.Avg for f, _ in aggs):
-            out = self.join_filter_aggregate_shuffle(probe_cols, probe_key_idx, predicate, build_key, build_group_keys,
-                                                     partial)
-            return self._finish_avg(out, recipe, partial, build_group_keys, probe_cols)
+        return self._with_avg(lambda a: self._shuffle_join(probe_cols, probe_key_idx, predicate, build_key,
+                                                           build_group_keys, a),
+                              aggs, build_group_keys, probe_cols)
+
+    def _shuffle_join(self, probe_cols, probe_key_idx, predicate, build_key, build_group_keys, aggs):
+        """join_filter_aggregate_shuffle over a request without AVG."""
         if self.world == 1:
             # one partition: both hash exchanges and the final merge are the identity, so the plan
             # is the local fused operator on this rank's rows
-            pk, pa_, g = self.ctx.join_filter_aggregate(probe_cols, probe_key_idx, predicate, build_key,
-                                                        build_group_keys, aggs)
-            if g == 0:
-                pk, pa_ = self._empty_partials(build_group_keys, probe_cols, aggs)
+            pk, pa_ = self._partials_or_empty(
+                self.ctx.join_filter_aggregate(probe_cols, probe_key_idx, predicate, build_key, build_group_keys, aggs),
+                build_group_keys, probe_cols, aggs)
             return self._final(pk, pa_, aggs)
         if self.device == "cuda" and len(build_group_keys) == 1 and not os.environ.get("QEH_NO_ITEMS_SHUFFLE"):
             out = self._shuffle_items(probe_cols, probe_key_idx, predicate, build_key, build_group_keys, aggs)
@@ -1143,10 +1171,9 @@ class DistributedExecutor:
         precv, _ = self._exchange_columns(pmoved, pcounts)
         brecv, _ = self._exchange_columns(bmoved, bcounts)
         local_aggs = [(f, remap[c]) for f, c in aggs]
-        pk, pa_, g = self.ctx.join_filter_aggregate(precv, remap[probe_key_idx], None, brecv[0], brecv[1:],
-                                                    local_aggs)
-        if g == 0:
-            pk, pa_ = self._empty_partials(build_group_keys, probe_cols, aggs)
+        pk, pa_ = self._partials_or_empty(
+            self.ctx.join_filter_aggregate(precv, remap[probe_key_idx], None, brecv[0], brecv[1:], local_aggs),
+            build_group_keys, probe_cols, aggs)
         return self._final(pk, pa_, aggs)
 
     def _shuffle_items(self, probe_cols, probe_key_idx, predicate, build_key, build_group_keys, aggs):
@@ -1160,54 +1187,18 @@ class DistributedExecutor:
         rows, and the wire carries 10 B per selected fact row instead of 16.  Decided from gathered
         values only; a declined plan or an overflow on any rank (gathered with the block totals), or a
         key on two ranks (the status lane), returns None on every rank (the two-pass form follows)."""
-        if (len(build_group_keys) != 1 or build_key.dtype != abi.DT_INT64
-                or build_group_keys[0].dtype not in (abi.DT_INT64, abi.DT_INT32)
-                or any(f not in (AF.Count, AF.Sum) for f, _ in aggs)):
+        if not _dense_join_schema(build_key, build_group_keys, aggs):
             return None
         gkc = build_group_keys[0]
         W, me = self.world, self.rank
-        local_ok = 1 if self.ctx.fused_items_check(probe_cols, probe_key_idx, predicate, aggs) else 0
-        bitmap = 1 if (build_key.c.validity or gkc.c.validity) else 0
-        row_len = 7  # [rows, key min, max, group key min, max, has-bitmap, shape ok]
-        row = torch.empty(row_len, dtype=torch.int64, device="cuda")
-        self._sync_torch()
-        self.ctx.broadcast_stats(build_key, gkc, [bitmap, local_ok], row.data_ptr())
-        self._sync()
-        out = torch.empty(W * row_len, dtype=torch.int64, device="cuda")
-        dist.all_gather_into_tensor(out, row, group=self.group)
-        row = out
-        pinned = getattr(self, "_shuffle_pinned", None)
-        if pinned is None or pinned.numel() != row.numel():
-            pinned = self._shuffle_pinned = torch.empty(row.numel(), dtype=torch.int64, pin_memory=True)
-        pinned.copy_(row, non_blocking=True)  # queued ahead of phase A
-        copied = torch.cuda.Event()
-        copied.record()
-        handle = None
-        if local_ok:
-            self._sync_torch()
-            try:
-                handle = self.ctx.shuffle_items_begin(probe_cols, probe_key_idx, predicate, aggs, row.data_ptr(), W,
-                                                      me, row_len)
-            except abi.QehError:
-                handle = None  # (this rank still joins the block-totals all-gather below, with ok = 0)
-        copied.synchronize()
-        M = pinned.numpy().reshape(W, row_len).copy()
-        live = M[M[:, 0] > 0]
-        n_sum = sum(1 for f, _ in aggs if f == AF.Sum)
-        ok = bool(M[:, 6].min() == 1 and M[:, 5].max() == 0 and int(M[:, 0].sum()) > 0)
-        if ok:
-            kmin, kmax = int(live[:, 1].min()), int(live[:, 2].max())
-            gmin, gmax = int(live[:, 3].min()), int(live[:, 4].max())
-            R, G = kmax - kmin + 1, gmax - gmin + 1
-            F = (R + (1 << 16) - 1) >> 16
-            ok = (1 <= F <= self.ITEMS_SLICES and G * (1 + n_sum) <= self.ITEMS_STATE_WORDS
-                  and 2 * R >= self.ITEMS_MIN_TABLE_BYTES)
-        if not ok:
-            if handle is not None:
-                self.ctx.fused_items_abort(handle)
+        opened = self._items_open(
+            lambda stats, row_len: self.ctx.shuffle_items_begin(probe_cols, probe_key_idx, predicate, aggs, stats, W,
+                                                                me, row_len),
+            probe_cols, probe_key_idx, predicate, build_key, gkc, aggs)
+        if opened is None:
             return None
+        handle, gmin, G, nb, span = opened
         # this rank's dimension rows grouped by slice, all-gathered (every rank builds only its own slices)
-        nb, span = self.ctx.fused_items_shape(int(M[:, 0].max()), W)
         OW = 2 * (self.ITEMS_SLICES + 1)
         items = torch.empty(nb * span, dtype=torch.int32, device="cuda")
         offs = torch.empty(nb * OW, dtype=torch.int32, device="cuda")
@@ -1239,34 +1230,24 @@ class DistributedExecutor:
         pin[me] = pout[me] = 0
         peak = _peak_remote(Mt[:, :W])
         starts = [q * blockcap for q in range(W)]
-        nacol = vp != 0
         # (received keys / values with slack: phase B's pair loads may read one item past a count; the
         # 16-bit keys travel as 32-bit pairs -- every block and total is even -- which gloo also carries)
         keys_t = torch.as_tensor(_DeviceView(kp, W * blockcap // 2, "<i4", handle))
         rk = _all_to_all(keys_t, [c // 2 for c in pin], [c // 2 for c in pout], peak // 2, self.group,
                          [x // 2 for x in starts], pad=2)
         rv = None
-        if nacol:
+        if vp != 0:  # (COUNT only: no value column)
             vals_t = torch.as_tensor(_DeviceView(vp, W * blockcap, "<i8", handle))
             rv = _all_to_all(vals_t, pin, pout, peak, self.group, starts, pad=4)
         cnt_t = torch.as_tensor(_DeviceView(cp, W * E, "<i4", handle))
         rc = _all_to_all(cnt_t, [E] * W, [E] * W, E, self.group)
         src_off = np.concatenate([[0], np.cumsum(pout)[:-1]]).astype(np.int64)
-        nl = (1 + len(aggs)) * G + 1
-        lanes = torch.empty(nl, dtype=torch.float64, device="cuda")
-        self._sync_torch()
-        self.ctx.shuffle_items_finish(handle, rk.data_ptr(), rv.data_ptr() if rv is not None else 0, rc.data_ptr(),
-                                      src_off, gi.data_ptr(), span, go.data_ptr(), W * nb, G, lanes.data_ptr())
-        self._sync()
-        dist.all_reduce(lanes, op=dist.ReduceOp.SUM, group=self.group)
-        self._sync_torch()
-        got, ov, g, bad = self.ctx.dense_states_take_status(
-            lanes.data_ptr(), len(aggs), gmin, G, W, me, gkc.dtype,
-            [abi.DT_INT64 if f == AF.Count else abi.DT_FLOAT64 for f, _ in aggs])
-        if bad != 0.0:
-            return None
-        self.last_final = "dense"
-        return [got], ov, g
+        # (a failing finish on this rank flags the lanes, as in the broadcast form: _items_finish)
+        return self._items_finish(
+            handle, lambda h, lanes: self.ctx.shuffle_items_finish(h, rk.data_ptr(), rv.data_ptr() if rv is not None else 0,
+                                                                   rc.data_ptr(), src_off, gi.data_ptr(), span,
+                                                                   go.data_ptr(), W * nb, G, lanes),
+            aggs, gmin, G, gkc.dtype)
 
     def _moved_shuffle_ok(self, part_keys, cols) -> bool:
         """The fused window shuffle applies: one non-null 16-B aligned Int64 PARTITION BY key, every
@@ -1292,6 +1273,20 @@ class DistributedExecutor:
         back, _ = self._exchange_columns([res], recv_counts)
         return self.ctx.partition_hash_unmove(part_keys[0], self.world, [back[0]])[0]
 
+    def _perm_window(self, part_keys, cols, local_fn, nulls: bool = False) -> DeviceColumn:
+        """The window shuffle for the shapes _moved_window does not take: a hash permutation, a take per
+        column, the exchange, the function on what arrived, the reverse all-to-all (each source gets
+        back what it sent), and the way back into input order -- a scatter through the permutation, or
+        with `nulls` (results that carry NULLs, LAG / LEAD / ...) a take through its inverse."""
+        counts, perm = self.ctx.hash_partition(part_keys[0], self.world)
+        recv, recv_counts = self._exchange_columns([self.ctx.take(c, perm) for c in cols], counts)
+        res = local_fn(recv)
+        back, _ = self._exchange_columns([res], recv_counts)
+        if not nulls:
+            return self.ctx.scatter(back[0], perm)
+        inv = self.ctx.scatter(self.ctx.upload(np.arange(len(part_keys[0]), dtype=np.uint32)), perm)
+        return self.ctx.take(back[0], inv)
+
     def row_number(self, part_keys: Sequence[DeviceColumn], order_keys: Sequence[DeviceColumn],
                    ascending: Sequence[bool]) -> DeviceColumn:
         """ROW_NUMBER() OVER (PARTITION BY .. ORDER BY ..) over rank-sharded rows
@@ -1303,17 +1298,9 @@ class DistributedExecutor:
         a scatter for shapes it does not take)."""
         cols = list(part_keys) + list(order_keys)
         _refuse_utf8_keys(cols, "window")
-        if self._moved_shuffle_ok(part_keys, cols):
-            npk = len(part_keys)
-            return self._moved_window(part_keys, cols,
-                                      lambda recv: self.ctx.row_number(recv[:npk], recv[npk:], list(ascending)))
-        counts, perm = self.ctx.hash_partition(part_keys[0], self.world)
-        cols = list(part_keys) + list(order_keys)
-        recv, recv_counts = self._exchange_columns([self.ctx.take(c, perm) for c in cols], counts)
         npk = len(part_keys)
-        rn = self.ctx.row_number(recv[:npk], recv[npk:], list(ascending))
-        back, _ = self._exchange_columns([rn], recv_counts)  # reverse: return what each source sent
-        return self.ctx.scatter(back[0], perm)
+        route = self._moved_window if self._moved_shuffle_ok(part_keys, cols) else self._perm_window
+        return route(part_keys, cols, lambda recv: self.ctx.row_number(recv[:npk], recv[npk:], list(ascending)))
 
     def window(self, func: int, part_keys: Sequence[DeviceColumn], order_keys: Sequence[DeviceColumn],
                ascending: Sequence[bool], arg: Optional[DeviceColumn] = None, param: int = 0,
@@ -1327,19 +1314,13 @@ class DistributedExecutor:
         _refuse_utf8_keys(list(part_keys) + list(order_keys), "window")
         cols = list(part_keys) + list(order_keys) + ([arg] if arg is not None else [])
         npk, nok = len(part_keys), len(order_keys)
+
+        def local_fn(recv):
+            return self.ctx.window(func, recv[:npk], recv[npk:npk + nok], list(ascending),
+                                   arg=recv[npk + nok] if arg is not None else None, param=param, default=default)
         if func in (W.RowNumber, W.Rank, W.DenseRank, W.Ntile) and self._moved_shuffle_ok(part_keys, cols):
-            # non-null Int64 results: back through the moved route
-            return self._moved_window(part_keys, cols, lambda recv: self.ctx.window(
-                func, recv[:npk], recv[npk:npk + nok], list(ascending),
-                arg=recv[npk + nok] if arg is not None else None, param=param, default=default))
-        counts, perm = self.ctx.hash_partition(part_keys[0], self.world)
-        recv, recv_counts = self._exchange_columns([self.ctx.take(c, perm) for c in cols], counts)
-        npk, nok = len(part_keys), len(order_keys)
-        res = self.ctx.window(func, recv[:npk], recv[npk:npk + nok], list(ascending),
-                              arg=recv[npk + nok] if arg is not None else None, param=param, default=default)
-        back, _ = self._exchange_columns([res], recv_counts)
-        inv = self.ctx.scatter(self.ctx.upload(np.arange(len(part_keys[0]), dtype=np.uint32)), perm)
-        return self.ctx.take(back[0], inv)
+            return self._moved_window(part_keys, cols, local_fn)  # non-null Int64 results
+        return self._perm_window(part_keys, cols, local_fn, nulls=True)
 
     def sort(self, cols: Sequence[DeviceColumn], key_idx: Sequence[int], ascending: Sequence[bool],
              samples_per_rank: int = 4096) -> List[DeviceColumn]:

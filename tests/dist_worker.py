@@ -573,6 +573,92 @@ def mode_gpu_devtensors(rank, world):
     ctx.close()
 
 
+def mode_gpu_items_fail(rank, world):
+    """A library error on one rank only, at every guarded step of both items forms: on rank 1 a stub
+    in place of one Context method raises QEH_E_OOM without calling the library (the finish calls
+    consume their handle, so their stubs free it first).  No rank may be left waiting in a collective:
+    every rank returns from the plan, every rank has left the items form for the one that follows
+    it, and the result is the oracle's.  The shapes are mode_gpu_devtensors's, which both items forms
+    take -- checked first, without a stub, or the cases would test nothing."""
+    import torch
+    import qe_hip
+    import oracle_bind as ob
+    from helpers import assert_grouped_equal
+    from qe_hip import AggregateFunction as AF, BinaryOp, abi, binop, col, lit
+    from qe_hip import distributed as D
+    torch.cuda.set_device(0)
+    s = torch.cuda.Stream()
+    torch.cuda.set_stream(s)
+    ctx = qe_hip.Context(0)
+    ctx.set_stream(s.cuda_stream)
+    dx = D.DistributedExecutor(ctx, device="cuda")
+    n, nd = 3_000_000, 4_000_000
+    x = ob.generate(abi_gen("UNIFORM_MOD"), 0x5EED, 1, n, 100, row0=rank * n)
+    kk = ob.generate(abi_gen("UNIFORM_MOD"), 0x5EED, 2, n, nd, row0=rank * n)
+    vv = ob.generate(abi_gen("UNIT_F64"), 0x5EED, 3, n, row0=rank * n)
+    dk_all = ob.generate(abi_gen("PERMUTATION"), 0x5EED, 0, nd, nd)
+    dg_all = ob.generate(abi_gen("UNIFORM_MOD"), 0x5EED, 5, nd, 1024)
+    b = np.linspace(0, nd, world + 1).astype(int)
+    pred = binop(col(0), BinaryOp.Greater, lit(49))
+    aggs = [(AF.Sum, 2), (AF.Count, 2)]
+    if rank == 0:  # the oracle's answer, once for every case
+        X = ob.generate(abi_gen("UNIFORM_MOD"), 0x5EED, 1, n * world, 100)
+        KK = ob.generate(abi_gen("UNIFORM_MOD"), 0x5EED, 2, n * world, nd)
+        VV = ob.generate(abi_gen("UNIT_F64"), 0x5EED, 3, n * world)
+        wk, wa, _ = ob.join_filter_aggregate([ob.HostCol(X), ob.HostCol(KK), ob.HostCol(VV)], 1, pred,
+                                             ob.HostCol(dk_all), [ob.HostCol(dg_all)], aggs)
+    fact = [ctx.upload(x), ctx.upload(kk), ctx.upload(vv)]
+    dk, dg = ctx.upload(dk_all[b[rank]:b[rank + 1]]), ctx.upload(dg_all[b[rank]:b[rank + 1]])
+
+    def broadcast():
+        return dx.join_filter_aggregate_broadcast(fact, 1, pred, dk, [dg], aggs, build_sharded=True)
+
+    def shuffle():
+        return dx.join_filter_aggregate_shuffle(fact, 1, pred, dk, [dg], aggs)
+
+    def check(out):
+        keys, aggs_out, _ = out
+        res = dx.gather_to_root(keys + aggs_out)
+        if rank == 0:
+            assert_grouped_equal(res[:1], res[1:], wk, wa, float_aggs=[0])
+
+    check(broadcast())
+    assert dx.last_build == "items", dx.last_build
+    check(shuffle())
+    assert dx.last_shuffle == "items", dx.last_shuffle
+    hits = []
+
+    def failing(name):
+        def stub(*args, **kwargs):
+            hits.append(name)
+            if name.endswith("_finish"):
+                ctx.fused_items_abort(args[0])
+            raise abi.QehError(abi.QEH_E_OOM, f"injected failure in {name}")
+        return stub
+
+    for plan, names in ((broadcast, ("fused_items_begin", "fused_items_build", "fused_items_finish")),
+                        (shuffle, ("shuffle_items_begin", "fused_items_build", "shuffle_items_pack",
+                                   "shuffle_items_finish"))):
+        for name in names:
+            del hits[:]
+            if rank == 1:
+                setattr(ctx, name, failing(name))
+            try:
+                out = plan()  # returns on every rank: an exception or a rank left in a collective fails the test
+            finally:
+                if rank == 1:
+                    delattr(ctx, name)
+            assert hits == ([name] if rank == 1 else []), (name, hits)
+            if plan is broadcast:
+                assert dx.last_build != "items", (name, dx.last_build)
+            else:
+                assert dx.last_shuffle == "two_pass", (name, dx.last_shuffle)
+            check(out)
+    torch.cuda.synchronize()
+    ctx.set_stream(0)
+    ctx.close()
+
+
 def abi_gen(name):
     from qe_hip import abi
     return getattr(abi, "GEN_" + name)
@@ -641,7 +727,7 @@ def main():
         {"exchange": mode_exchange, "exchange_bytes": mode_exchange_bytes, "exchange_chunked": mode_exchange_chunked,
          "gpu": mode_gpu,
          "gpu_exchange": mode_gpu_exchange, "gpu_cfg4": mode_gpu_cfg4, "nccl1": mode_nccl1,
-         "gpu_devtensors": mode_gpu_devtensors}[mode](rank, world)
+         "gpu_devtensors": mode_gpu_devtensors, "gpu_items_fail": mode_gpu_items_fail}[mode](rank, world)
         dist.barrier()
     finally:
         dist.destroy_process_group()

@@ -136,6 +136,15 @@ def test_device_tensor_collectives_several_ranks_on_one_gpu(world):
 
 
 @pytest.mark.gpu
+def test_items_forms_survive_one_rank_failing():
+    """A library error (an injected QEH_E_OOM) on rank 1 only, in turn at begin, build and finish of
+    the broadcast join's items form and at begin, build, pack and finish of the shuffle join's: both
+    ranks return from the plan (a rank left in a collective runs into the launch timeout), both have
+    left the items form, and the form that follows gives the oracle's SUM and COUNT."""
+    launch("gpu_items_fail", 2, timeout=180)
+
+
+@pytest.mark.gpu
 def test_rccl_world_size_one():
     """The "nccl" backend (RCCL) with world_size 1 on the GPU: exchange, shuffle join,
     partial/final GROUP BY, the sharded broadcast join and config 4's shuffle join vs the oracle."""
