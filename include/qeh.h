@@ -689,6 +689,22 @@ int qeh_hash_partition(qeh_ctx *ctx, const qeh_column *key, int n_parts, int64_t
 int qeh_range_partition(qeh_ctx *ctx, const qeh_column *key, int ascending, const int64_t *splitters,
                         int n_splitters, int64_t *counts, qeh_column *out_perm);
 
+/* qeh_range_partition for a Utf8 key (distributed ORDER BY on strings): the splitters are
+ * n_splitters (0..255) strings in host memory, splitter j = splitter_bytes[splitter_offsets[j] ..
+ * splitter_offsets[j+1]); splitter_offsets has n_splitters + 1 entries, starts at 0 and never
+ * decreases; the splitters are in ascending order (equal neighbours allowed).  The order is byte-wise
+ * unsigned lexicographic with a proper prefix before any longer string -- the order qeh_sort_indices
+ * gives a Utf8 key and the order of qeh_utf8_dict_encode's codes.  A NULL row goes to partition 0;
+ * ascending: a row's partition is the number of splitters strictly less than its string; descending:
+ * the number strictly greater; so a string equal to a splitter lands in the lower of the two
+ * partitions the splitter separates.  counts[n_splitters + 1] and the stable partition-major UINT32
+ * `out_perm` as qeh_hash_partition.  The column is streamed once against the splitters (no
+ * dictionary), so ranks that share the splitters partition alike.  QEH_E_INVALID: null pointers,
+ * n_splitters outside 0..255, malformed offsets, splitters out of order; QEH_E_UNSUPPORTED: a key
+ * that is not Utf8 (qeh_range_partition takes those). */
+int qeh_range_partition_utf8(qeh_ctx *ctx, const qeh_column *key, int ascending, const int32_t *splitter_offsets,
+                             const uint8_t *splitter_bytes, int n_splitters, int64_t *counts, qeh_column *out_perm);
+
 /* Partitioner::partition_by_hash over several key columns (distributed/partition.rs:151-212):
  * a partition-major permutation, stable within a partition, with per-partition row counts.
  * Int32 / Int64 / Utf8 keys; NULL cells are skipped when hashing, as compute_row_hash does

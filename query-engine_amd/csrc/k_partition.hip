@@ -6,6 +6,7 @@
 // (crates/query-distributed/src/partition.rs:151-212) with a device hash; range partitioning
 // find_range_partition (partition.rs:320-341).
 #include <algorithm>
+#include <cstring>
 #include <string>
 #include <vector>
 
@@ -403,6 +404,90 @@ __global__ void k_range_ids(ColRef key, int64_t n, const int64_t *__restrict__ s
     }
 }
 
+// ---- range partition by strings (qeh_range_partition_utf8) --------------------------------------
+// k_range_ids for a Utf8 key against up to 255 splitter strings, in the byte-wise unsigned order of
+// k_utf8_cmp and of the codes of qeh_utf8_dict_encode (a proper prefix before any longer string).
+// Every workgroup keeps, per splitter, its first 8 bytes packed big-endian into one word (zero past
+// the end; k_dict_pack's packing) and its byte range in LDS.  A row packs its own first 8 bytes the
+// same way and binary-searches the words (at most 8 steps); only where the two words tie are more
+// bytes compared: by length when either string ends inside the word, else 8 bytes at a time from
+// byte 8 on.  The splitter bytes live in LDS when all of them fit kRpLdsBytes (LDS = true), else they
+// are read from global memory (255 splitters of any length).  NULL rows read no bytes; one row per
+// lane, no lane waits on another; every loop is bounded by the splitter count or a string's length.
+constexpr int kRpMaxSplit = kRadix - 1;
+constexpr int kRpLdsBytes = 16 * 1024;  // splitter bytes kept in LDS (+ 2 KiB words, 1 KiB offsets)
+
+struct Utf8KeyIn {
+    ColRef valid;         // validity only
+    const int32_t *offs;  // advanced by the column offset
+    const uint8_t *data;
+};
+
+// bytes [0, min(rem, 8)) at p as one big-endian word, zero past the end; reads no other byte
+__device__ __forceinline__ uint64_t rp_word(const uint8_t *p, int32_t rem) {
+    uint64_t w = 0;
+    if (rem >= 8) {
+        __builtin_memcpy(&w, p, 8);
+    } else {
+#pragma unroll
+        for (int b = 0; b < 7; ++b)
+            if (b < rem) w |= (uint64_t)p[b] << (8 * b);
+    }
+    return __builtin_bswap64(w);
+}
+
+// the order of splitter `sp` (sl bytes, first word sw) against the row `rp` (rl bytes, first word rw):
+// < 0 splitter first, 0 equal, > 0 row first
+__device__ __forceinline__ int rp_cmp(uint64_t sw, const uint8_t *sp, int32_t sl, uint64_t rw, const uint8_t *rp, int32_t rl) {
+    if (sw != rw) return sw < rw ? -1 : 1;
+    const int32_t m = sl < rl ? sl : rl;
+    // equal words and a string that ends inside them: the common prefix is equal and the longer
+    // string continues with 0x00 bytes only (inside the word), so the shorter one sorts first
+    for (int32_t o = 8; o < m; o += 8) {
+        const uint64_t a = rp_word(sp + o, m - o), b = rp_word(rp + o, m - o);
+        if (a != b) return a < b ? -1 : 1;
+    }
+    return sl < rl ? -1 : (sl > rl ? 1 : 0);
+}
+
+template <bool LDS>
+__global__ __launch_bounds__(kBlock) void k_range_ids_utf8(Utf8KeyIn key, int64_t n, const int32_t *__restrict__ sp_offs,
+                                                           const uint8_t *__restrict__ sp_bytes, int n_split, int asc,
+                                                           uint64_t *__restrict__ ids, uint32_t *__restrict__ idx) {
+    __shared__ uint64_t s_word[kRpMaxSplit + 1];
+    __shared__ int32_t s_off[kRpMaxSplit + 2];
+    __shared__ uint32_t s_bytes[LDS ? kRpLdsBytes / 4 : 2];
+    for (int j = threadIdx.x; j <= n_split; j += kBlock) s_off[j] = sp_offs[j];
+    __syncthreads();
+    for (int j = threadIdx.x; j < n_split; j += kBlock) s_word[j] = rp_word(sp_bytes + s_off[j], s_off[j + 1] - s_off[j]);
+    if (LDS) {  // whole words: the host pads the device copy of the bytes to a multiple of 4 and checked the fit
+        const int32_t words = ((s_off[n_split] < kRpLdsBytes ? s_off[n_split] : kRpLdsBytes) + 3) / 4;
+        for (int32_t w = threadIdx.x; w < words; w += kBlock) s_bytes[w] = ((const uint32_t *)sp_bytes)[w];
+    }
+    __syncthreads();
+    const uint8_t *sb = LDS ? (const uint8_t *)s_bytes : sp_bytes;
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) {
+        uint32_t p = 0;  // NULL -> 0, as k_range_ids
+        if (col_valid(key.valid, i)) {
+            const int32_t s = key.offs[i], len = key.offs[i + 1] - s;
+            const uint8_t *rp = key.data + s;
+            const uint64_t rw = rp_word(rp, len);
+            // ascending: the splitters strictly below the row = the first splitter >= it;
+            // descending: the splitters strictly above it = n_split - the first splitter > it
+            int lo = 0, hi = n_split;
+            for (int step = 0; step < 8 && lo < hi; ++step) {  // 2^8 > kRpMaxSplit
+                const int mid = (lo + hi) >> 1;
+                const int c = rp_cmp(s_word[mid], sb + s_off[mid], s_off[mid + 1] - s_off[mid], rw, rp, len);
+                if (asc ? c < 0 : c <= 0) lo = mid + 1;
+                else hi = mid;
+            }
+            p = (uint32_t)(asc ? lo : n_split - lo);
+        }
+        ids[i] = p;
+        idx[i] = (uint32_t)i;
+    }
+}
+
 // PartitionStrategy::Hash over several key columns (partition.rs:151-212, compute_row_hash
 // :292-316): NULL cells contribute nothing to the row hash, as the reference skips them; Int32 /
 // Int64 values and Utf8 bytes are mixed into one 64-bit hash (the hash function is not
@@ -645,6 +730,51 @@ extern "C" int qeh_range_partition(qeh_ctx *ctx, const qeh_column *key, int asce
                                sp.as<int64_t>(), n_splitters, ascending ? 1 : 0, ids, idx);
         },
         "range_partition", counts, out_perm);
+}
+
+extern "C" int qeh_range_partition_utf8(qeh_ctx *ctx, const qeh_column *key, int ascending, const int32_t *splitter_offsets,
+                                        const uint8_t *splitter_bytes, int n_splitters, int64_t *counts,
+                                        qeh_column *out_perm) {
+    if (!ctx || !key || !counts || !out_perm || !splitter_offsets || n_splitters < 0 || n_splitters > kRpMaxSplit)
+        return fail(QEH_E_INVALID, "qeh_range_partition_utf8: bad argument (0..255 splitters)");
+    if (splitter_offsets[0] != 0) return fail(QEH_E_INVALID, "qeh_range_partition_utf8: splitter offsets must start at 0");
+    for (int j = 0; j < n_splitters; ++j)
+        if (splitter_offsets[j + 1] < splitter_offsets[j])
+            return fail(QEH_E_INVALID, "qeh_range_partition_utf8: splitter offsets must not decrease");
+    const int32_t total = splitter_offsets[n_splitters];
+    if (total > 0 && !splitter_bytes) return fail(QEH_E_INVALID, "qeh_range_partition_utf8: bad argument (no splitter bytes)");
+    for (int j = 1; j < n_splitters; ++j) {  // byte-wise unsigned, a proper prefix first
+        const int32_t a = splitter_offsets[j - 1], b = splitter_offsets[j], c = splitter_offsets[j + 1];
+        const int32_t la = b - a, lb = c - b, m = std::min(la, lb);
+        const int d = m > 0 ? std::memcmp(splitter_bytes + a, splitter_bytes + b, (size_t)m) : 0;
+        if (d > 0 || (d == 0 && la > lb))
+            return fail(QEH_E_INVALID, "qeh_range_partition_utf8: splitters must be ascending");
+    }
+    DeviceGuard dg(ctx->device);
+    QEH_TRY(check_column(*key, "partition key"));
+    if (key->dtype != QEH_DT_UTF8)
+        return fail(QEH_E_UNSUPPORTED, "qeh_range_partition_utf8: the key must be Utf8 (qeh_range_partition takes the other types)");
+    const int64_t n = key->length;
+    if (n > 0 && !key->offsets) return fail(QEH_E_INVALID, "partition key: null offsets pointer");
+    DevBuf so, sb;
+    QEH_TRY(so.alloc(ctx, (size_t)(n_splitters + 1) * 4));
+    QEH_TRY(sb.alloc(ctx, (size_t)total + 8));  // (whole words past the end for the copy into LDS)
+    QEH_HIP(hipMemcpyAsync(so.p, splitter_offsets, (size_t)(n_splitters + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
+    if (total > 0) QEH_HIP(hipMemcpyAsync(sb.p, splitter_bytes, (size_t)total, hipMemcpyHostToDevice, ctx->stream));
+    QEH_HIP(hipStreamSynchronize(ctx->stream));  // the host splitter arrays may go away
+    Utf8KeyIn in{};
+    in.valid = make_colref(*key);
+    in.offs = key->offsets + key->offset;
+    in.data = (const uint8_t *)key->values;
+    const bool lds = total <= kRpLdsBytes;
+    return partition_perm(
+        ctx, n, n_splitters + 1,
+        [&](uint64_t *ids, uint32_t *idx) {
+            hipLaunchKernelGGL(lds ? k_range_ids_utf8<true> : k_range_ids_utf8<false>, dim3(grid_for(ctx, n, kBlock * 4, 8)),
+                               dim3(kBlock), 0, ctx->stream, in, n, so.as<int32_t>(), sb.as<uint8_t>(), n_splitters,
+                               ascending ? 1 : 0, ids, idx);
+        },
+        "range_partition_utf8", counts, out_perm);
 }
 
 extern "C" int qeh_partition_hash(qeh_ctx *ctx, const qeh_column *keys, int n_keys, int n_parts, int64_t *counts,

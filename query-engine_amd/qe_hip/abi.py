@@ -151,6 +151,7 @@ SIGNATURES = {
     "qeh_window": (I, [P, I, COLP, I, COLP, I, C.POINTER(C.c_int8), COLP, I64, C.POINTER(I64), COLP]),
     "qeh_hash_partition": (I, [P, COLP, I, C.POINTER(I64), COLP]),
     "qeh_range_partition": (I, [P, COLP, I, C.POINTER(I64), I, C.POINTER(I64), COLP]),
+    "qeh_range_partition_utf8": (I, [P, COLP, I, C.POINTER(C.c_int32), C.POINTER(C.c_uint8), I, C.POINTER(I64), COLP]),
     "qeh_scatter": (I, [P, COLP, COLP, COLP]),
     "qeh_validity_to_bytes": (I, [P, COLP, P]),
     "qeh_bytes_to_validity": (I, [P, P, I64, P]),

@@ -107,18 +107,23 @@ class DeviceColumn:
         raw = data.tobytes()
         return [raw[offs[i]:offs[i + 1]] for i in range(n)]
 
+    def valid_mask(self) -> Optional[np.ndarray]:
+        """The validity bitmap as bool[n] on the host; None without a bitmap."""
+        n, off = self.c.length, self.c.offset
+        if not self.c.validity:
+            return None
+        if n == 0:
+            return np.zeros(0, bool)
+        nbytes = (off + n + 7) // 8
+        vb = np.empty(nbytes, np.uint8)
+        self.ctx.d2h(vb, self.c.validity, nbytes)
+        return unpack_bits(vb, n, off)
+
     def to_numpy(self) -> Tuple[np.ndarray, Optional[np.ndarray]]:
         """(values, validity-or-None) copied to the host."""
         n, off = self.c.length, self.c.offset
         ctx = self.ctx
-        valid = None
-        if self.c.validity and n > 0:
-            nbytes = (off + n + 7) // 8
-            vb = np.empty(nbytes, np.uint8)
-            ctx.d2h(vb, self.c.validity, nbytes)
-            valid = unpack_bits(vb, n, off)
-        elif self.c.validity:
-            valid = np.zeros(0, bool)
+        valid = self.valid_mask()
         if self.c.dtype == abi.DT_UTF8:
             offs = np.empty(n + 1, np.int32)
             ctx.d2h(offs, self.c.offsets + 4 * off, 4 * (n + 1))
@@ -305,7 +310,11 @@ class Context:
         return DeviceColumn(self, c, bufs)
 
     def empty(self, dtype: int, n: int) -> DeviceColumn:
-        """Uninitialised device column (no validity) from the pool."""
+        """Uninitialised device column (no validity) from the pool.  Utf8: zero rows only."""
+        if dtype == abi.DT_UTF8:
+            if n != 0:
+                raise ValueError("an uninitialised Utf8 column has no offsets: only n == 0")
+            return self._upload_utf8([])
         item = np.dtype(NP_OF[abi.physical_dtype(dtype)]).itemsize
         p = self.alloc(max(n * item, 8))
         c = abi.QehColumn(dtype=dtype, owned=0, length=n, offset=0, null_count=0, values=p)
@@ -908,6 +917,14 @@ class Context:
         abi.check(self.lib.qeh_hash_partition(self.h, C.byref(key.c), n_parts, counts, C.byref(out)))
         return np.array(counts[:], dtype=np.int64), self._wrap(out)
 
+    def partition_hash(self, keys: Sequence[DeviceColumn], n_parts: int):
+        """qeh_partition_hash: (counts, stable partition-major permutation) by the row hash of
+        Int32 / Int64 / Utf8 key columns."""
+        counts = (C.c_int64 * n_parts)()
+        out = abi.QehColumn()
+        abi.check(self.lib.qeh_partition_hash(self.h, self._cols(keys), len(keys), n_parts, counts, C.byref(out)))
+        return np.array(counts[:], dtype=np.int64), self._wrap(out)
+
     def range_partition(self, key: DeviceColumn, splitters, ascending: bool = True):
         """Partition ids by order-key ranges (qeh_range_partition); splitters
         are ascending order keys (see ``order_keys``)."""
@@ -918,6 +935,22 @@ class Context:
         abi.check(self.lib.qeh_range_partition(self.h, C.byref(key.c), 1 if ascending else 0,
                                                sp.ctypes.data_as(C.POINTER(C.c_int64)), len(sp), counts,
                                                C.byref(out)))
+        return np.array(counts[:], dtype=np.int64), self._wrap(out)
+
+    def range_partition_utf8(self, key: DeviceColumn, splitters: Sequence[bytes], ascending: bool = True):
+        """Partition ids of a Utf8 key by string ranges (qeh_range_partition_utf8): `splitters` are
+        `bytes` in ascending byte order (Python's order on bytes).  (counts, permutation)."""
+        sp = [bytes(s) for s in splitters]
+        offs = np.zeros(len(sp) + 1, np.int32)
+        if sp:
+            offs[1:] = np.cumsum([len(s) for s in sp])
+        raw = np.frombuffer(b"".join(sp) + b"\0" * 8, np.uint8)
+        counts = (C.c_int64 * (len(sp) + 1))()
+        out = abi.QehColumn()
+        abi.check(self.lib.qeh_range_partition_utf8(self.h, C.byref(key.c), 1 if ascending else 0,
+                                                    offs.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                    raw.ctypes.data_as(C.POINTER(C.c_uint8)), len(sp), counts,
+                                                    C.byref(out)))
         return np.array(counts[:], dtype=np.int64), self._wrap(out)
 
     def scatter(self, col: DeviceColumn, perm: DeviceColumn) -> DeviceColumn:

@@ -19,6 +19,10 @@ stages run for real:
   * row_number: hash shuffle by the partition key, local ROW_NUMBER, reverse
     all-to-all, scatter back into input order.
   * sort: sample splitters, range partition, exchange, stable local sort.
+  * keys of group_by, row_number, window, sort and hash_join_inner may be Utf8 (hashed by their
+    bytes; ranged against shared splitter strings by qeh_range_partition_utf8) or temporal (handed
+    to the partitioning calls as views of their physical integers, _physical); temporal columns
+    travel as those integers and get their dtype back on arrival.
   * join_filter_aggregate_broadcast (the BASELINE metric path): the dimension
     is replicated (broadcast join), every rank runs the fused kernel on its
     fact shard, then the partial states are shuffled by group key and merged.
@@ -170,11 +174,39 @@ def _all_to_all(p: torch.Tensor, pin: Sequence[int], pout: Sequence[int], peak: 
     return out
 
 
-def _refuse_utf8_keys(keys: Sequence[DeviceColumn], what: str) -> None:
-    """Utf8 keys are a single-device feature: a distributed operator would need one dictionary
-    shared by the ranks' columns."""
-    if any(k.dtype == abi.DT_UTF8 for k in keys):
-        raise abi.QehError(abi.QEH_E_UNSUPPORTED, f"Utf8 {what} keys are not supported in the distributed layer")
+def _refuse_join_plan_keys(world: int, probe_key: DeviceColumn, build_key: DeviceColumn,
+                           build_group_keys: Sequence[DeviceColumn], build_moves: bool) -> None:
+    """The key types the fused join plans (join_filter_aggregate_broadcast / _shuffle) do not take,
+    refused from the schema alone -- the same on every rank -- before the plan's first collective:
+    a Utf8 join key (the fused operator joins integers), and across ranks a temporal group key or,
+    where the build side moves (`build_moves`: a sharded dimension, the shuffle join), a temporal
+    join key.  group_by and hash_join_inner take these keys."""
+    if probe_key.dtype == abi.DT_UTF8 or build_key.dtype == abi.DT_UTF8:
+        raise abi.QehError(abi.QEH_E_UNSUPPORTED, "hash join keys must be Int32/Int64 on the device")
+    if world == 1:
+        return
+    if any(k.dtype in abi.TEMPORAL_DTYPES for k in build_group_keys):
+        raise abi.QehError(abi.QEH_E_UNSUPPORTED,
+                           "temporal group keys are not supported by the distributed join plans")
+    if build_moves and (probe_key.dtype in abi.TEMPORAL_DTYPES or build_key.dtype in abi.TEMPORAL_DTYPES):
+        raise abi.QehError(abi.QEH_E_UNSUPPORTED,
+                           "temporal join keys are not supported by the distributed join plans")
+
+
+def _physical(ctx: Context, col: DeviceColumn) -> DeviceColumn:
+    """A non-owning view of a temporal column with its physical integer dtype (Date32: Int32, Date64 /
+    Timestamp: Int64), the column itself otherwise: what the partitioning calls take as a key.  Equal
+    values hash and range alike, so rows with equal keys share a rank; the operator on the owning rank
+    gets the column with its own dtype."""
+    if col.dtype not in abi.TEMPORAL_DTYPES:
+        return col
+    c = abi.QehColumn()
+    C.pointer(c)[0] = col.c
+    c.owned = 0
+    c.dtype = abi.physical_dtype(col.dtype)
+    d = DeviceColumn(ctx, c)
+    d.parent = col
+    return d
 
 
 def _without_bitmap(ctx: Context, col: DeviceColumn) -> DeviceColumn:
@@ -318,10 +350,9 @@ class DistributedExecutor:
 
     def _to_tensors(self, col: DeviceColumn) -> List[torch.Tensor]:
         """Column -> payload tensors: values (Boolean: a byte per row; Utf8: int32 lengths, then
-        the bytes), then validity bytes when the column has a bitmap."""
+        the bytes; a temporal column: its physical integers, Date32 as int32, the others as int64),
+        then validity bytes when the column has a bitmap."""
         n = len(col)
-        if col.dtype in abi.TEMPORAL_DTYPES:  # the partitioner's rules for these types are not ported yet
-            raise abi.QehError(abi.QEH_E_UNSUPPORTED, "temporal columns are not supported by the distributed layer")
         if col.dtype in (abi.DT_UTF8, abi.DT_BOOL):
             if self.device == "cuda":
                 if col.dtype == abi.DT_BOOL:
@@ -348,11 +379,12 @@ class DistributedExecutor:
             if col.c.validity:
                 out.append(torch.from_numpy(m.astype(np.uint8)))
             return out
-        tdt = TORCH_OF[col.dtype]
+        pdt = abi.physical_dtype(col.dtype)
+        tdt = TORCH_OF[pdt]
         if self.device == "cuda":
             item = torch.empty(0, dtype=tdt).element_size()
             if n:  # a zero-copy view of the column's values (the view keeps the column alive)
-                vals = torch.as_tensor(_DeviceView(col.c.values + col.c.offset * item, n, TYPESTR[col.dtype], col),
+                vals = torch.as_tensor(_DeviceView(col.c.values + col.c.offset * item, n, TYPESTR[pdt], col),
                                        device="cuda")
             else:
                 vals = torch.empty(0, dtype=tdt, device="cuda")
@@ -363,6 +395,8 @@ class DistributedExecutor:
                 out.append(vb)
             return out
         v, m = col.to_numpy()
+        if v.dtype.kind == "M":  # datetime64 of the dtype's unit -> the physical integers
+            v = v.view(np.int64).astype(NP_OF[pdt])
         out = [torch.from_numpy(np.ascontiguousarray(v))]
         if col.c.validity:
             out.append(torch.from_numpy(m.astype(np.uint8)))
@@ -383,9 +417,10 @@ class DistributedExecutor:
             d = self.ctx.wrap_device(dtype, keep[0].data_ptr(), n, bitmap)
             d.parent = keep  # the torch buffers live as long as the column
             return d
-        v = vals.numpy().astype(NP_OF[dtype], copy=False)
+        v = vals.numpy().astype(NP_OF[abi.physical_dtype(dtype)], copy=False)
         m = None if valid is None else valid.numpy().astype(bool)
-        return self.ctx.upload(v, m)
+        # (a temporal column arrived as its physical integers and gets its own dtype back)
+        return self.ctx.upload(v, m, dtype=dtype if dtype in abi.TEMPORAL_DTYPES else None)
 
     def _bytes_to_bits(self, b: torch.Tensor) -> torch.Tensor:
         n = b.shape[0]
@@ -494,8 +529,9 @@ class DistributedExecutor:
         return out, sout
 
     def shuffle(self, key: DeviceColumn, cols: Sequence[DeviceColumn]) -> List[DeviceColumn]:
-        """Route every row to rank hash(key) % world (partition.rs:151-212)."""
-        counts, moved = self.ctx.partition_hash_move([key], self.world, cols)  # one device pass
+        """Route every row to rank hash(key) % world (partition.rs:151-212).  Int32 / Int64 / Utf8 keys
+        (FNV over a string's bytes: the same on every rank); a temporal key as its physical integers."""
+        counts, moved = self.ctx.partition_hash_move([_physical(self.ctx, key)], self.world, cols)  # one device pass
         out, _ = self._exchange_columns(moved, counts)
         return out
 
@@ -523,9 +559,20 @@ class DistributedExecutor:
     # ---- operators -----------------------------------------------------------------
     def hash_join_inner(self, probe_key_idx: int, probe_cols: Sequence[DeviceColumn], build_key_idx: int,
                         build_cols: Sequence[DeviceColumn]):
-        """Shuffle join: both sides hash-partitioned by the key, local device join."""
-        p = self.shuffle(probe_cols[probe_key_idx], probe_cols)
-        b = self.shuffle(build_cols[build_key_idx], build_cols)
+        """Shuffle join: both sides hash-partitioned by the key, local device join.  Int32 / Int64
+        keys, two temporal keys of one dtype, or two Utf8 keys (joined by qeh_hash_join on the rank
+        both strings hash to).  Keys the local join does not compare -- Utf8 against anything else,
+        two different temporal dtypes -- are its type error, raised before the first collective."""
+        pk, bk = probe_cols[probe_key_idx], build_cols[build_key_idx]
+        utf8 = pk.dtype == abi.DT_UTF8 or bk.dtype == abi.DT_UTF8
+        if pk.dtype != bk.dtype and (utf8 or pk.dtype in abi.TEMPORAL_DTYPES or bk.dtype in abi.TEMPORAL_DTYPES):
+            # the join's own refusal, from the dtypes alone (zero-row views: no data is read)
+            zp, zb = self.ctx.slice(pk, 0, 0), self.ctx.slice(bk, 0, 0)
+            self.ctx.hash_join(0, zp, [zp], zb, [zb])
+        p = self.shuffle(pk, probe_cols)
+        b = self.shuffle(bk, build_cols)
+        if utf8:
+            return self.ctx.hash_join(0, p[probe_key_idx], p, b[build_key_idx], b)
         return self.ctx.hash_join_inner(p[probe_key_idx], p, b[build_key_idx], b)
 
     def _final(self, keys: Sequence[DeviceColumn], partials: Sequence[DeviceColumn], aggs: Sequence[Tuple[int, int]]):
@@ -544,9 +591,10 @@ class DistributedExecutor:
         final aggregate on the owning rank.  Each rank returns the groups it owns.
         AVG travels as SUM + COUNT partials and is divided after the final merge (expand_avg,
         _finish_avg).  Results equal qeh_hash_aggregate over the concatenated shards, except that
-        float sums associate differently (per rank, then across ranks)."""
+        float sums associate differently (per rank, then across ranks).  Keys of every type the local
+        aggregate groups by, Utf8 and temporal included: the shuffle hashes a string's bytes and a
+        temporal key's physical integers."""
         def plan(aggs):
-            _refuse_utf8_keys(keys, "group")
             pk, pa_ = self._partials_or_empty(self.ctx.hash_aggregate(keys, inputs, aggs), keys, inputs, aggs)
             return self._final(pk, pa_, aggs)
         return self._with_avg(plan, aggs, keys, inputs, max_partials=None)  # (qeh_hash_aggregate chunks long lists)
@@ -673,7 +721,9 @@ class DistributedExecutor:
         AVG travels as SUM + COUNT partials through whichever form runs and is divided after the
         final merge (expand_avg, _finish_avg): AVG of a non-null Float64 column is a float-SUM lane and
         a COUNT lane, so it stays on the fast forms.  Results equal the single-device operator over the
-        concatenated shards, except that float sums associate differently."""
+        concatenated shards, except that float sums associate differently.  Key types outside the plan:
+        _refuse_join_plan_keys."""
+        _refuse_join_plan_keys(self.world, probe_cols[probe_key_idx], build_key, build_group_keys, build_sharded)
         return self._with_avg(lambda a: self._broadcast_join(probe_cols, probe_key_idx, predicate, build_key,
                                                              build_group_keys, a, build_sharded),
                               aggs, build_group_keys, probe_cols)
@@ -1128,7 +1178,8 @@ class DistributedExecutor:
              one all-to-all per column, so every key's probe and build rows meet on one rank;
           3. the local fused join + aggregate runs on what arrived, and the partial per-group
              states are shuffled by group key and merged on the owning rank.
-        AVG as in join_filter_aggregate_broadcast."""
+        AVG as in join_filter_aggregate_broadcast; key types outside the plan: _refuse_join_plan_keys."""
+        _refuse_join_plan_keys(self.world, probe_cols[probe_key_idx], build_key, build_group_keys, True)
         return self._with_avg(lambda a: self._shuffle_join(probe_cols, probe_key_idx, predicate, build_key,
                                                            build_group_keys, a),
                               aggs, build_group_keys, probe_cols)
@@ -1277,8 +1328,14 @@ class DistributedExecutor:
         """The window shuffle for the shapes _moved_window does not take: a hash permutation, a take per
         column, the exchange, the function on what arrived, the reverse all-to-all (each source gets
         back what it sent), and the way back into input order -- a scatter through the permutation, or
-        with `nulls` (results that carry NULLs, LAG / LEAD / ...) a take through its inverse."""
-        counts, perm = self.ctx.hash_partition(part_keys[0], self.world)
+        with `nulls` (results that carry NULLs, LAG / LEAD / ...) a take through its inverse.  A Utf8
+        first partition key is hashed by qeh_partition_hash (FNV over the bytes), an integer one by
+        qeh_hash_partition, a temporal one as its physical integers."""
+        k0 = _physical(self.ctx, part_keys[0])
+        if k0.dtype == abi.DT_UTF8:
+            counts, perm = self.ctx.partition_hash([k0], self.world)
+        else:
+            counts, perm = self.ctx.hash_partition(k0, self.world)
         recv, recv_counts = self._exchange_columns([self.ctx.take(c, perm) for c in cols], counts)
         res = local_fn(recv)
         back, _ = self._exchange_columns([res], recv_counts)
@@ -1295,9 +1352,9 @@ class DistributedExecutor:
         there (received order = source-rank-major, stable within a source, i.e. the
         global input order that breaks ties); the numbers go back by the reverse
         all-to-all into this rank's input order (_moved_window, or a permutation and
-        a scatter for shapes it does not take)."""
+        a scatter for shapes it does not take).  Utf8 and temporal partition and order keys take the
+        permutation form."""
         cols = list(part_keys) + list(order_keys)
-        _refuse_utf8_keys(cols, "window")
         npk = len(part_keys)
         route = self._moved_window if self._moved_shuffle_ok(part_keys, cols) else self._perm_window
         return route(part_keys, cols, lambda recv: self.ctx.row_number(recv[:npk], recv[npk:], list(ascending)))
@@ -1311,7 +1368,6 @@ class DistributedExecutor:
         through the inverse permutation (the results of LAG/LEAD/… carry NULLs)."""
         if not part_keys:
             raise ValueError("distributed window functions need a PARTITION BY key")
-        _refuse_utf8_keys(list(part_keys) + list(order_keys), "window")
         cols = list(part_keys) + list(order_keys) + ([arg] if arg is not None else [])
         npk, nok = len(part_keys), len(order_keys)
 
@@ -1327,22 +1383,36 @@ class DistributedExecutor:
         """ORDER BY over rank-sharded rows: range-partition on the first sort key
         with splitters from an all-gathered sample, then a stable local sort.  The
         global result is rank 0's rows, then rank 1's, ...  Equal first keys share a
-        rank and arrive source-rank-major, so the result is stable."""
+        rank and arrive source-rank-major, so the result is stable.  A Utf8 first key is sampled as
+        raw bytes and ranged by qeh_range_partition_utf8 against splitter strings, in the byte order the
+        local sort gives it; a temporal first key by its physical integers.  Fewer distinct keys than
+        ranks (or none that is not NULL) leave some ranks without rows."""
         k0 = cols[key_idx[0]]
         n = len(k0)
-        sample = np.empty(0, np.int64)
+        utf8 = k0.dtype == abi.DT_UTF8
+        sample = [] if utf8 else np.empty(0, np.int64)
         if n:
             idx = np.unique(np.linspace(0, n - 1, min(n, samples_per_rank)).astype(np.uint32))
-            sv, sm = self.ctx.take(k0, self.ctx.upload(idx)).to_numpy()
-            sample = order_keys(sv if sm is None else sv[sm])
+            taken = self.ctx.take(k0, self.ctx.upload(idx))
+            if utf8:
+                sm = taken.valid_mask()
+                sample = [b for b, ok in zip(taken.to_bytes(), np.ones(len(taken), bool) if sm is None else sm) if ok]
+            else:
+                sv, sm = taken.to_numpy()
+                if sv.dtype.kind == "M":
+                    sv = sv.view(np.int64)
+                sample = order_keys(sv if sm is None else sv[sm])
         objs = [None] * self.world
         dist.all_gather_object(objs, sample, group=self.group)
-        allk = np.sort(np.concatenate(objs)) if objs else np.empty(0, np.int64)
-        if len(allk):
-            splitters = allk[[(i + 1) * len(allk) // self.world for i in range(self.world - 1)]]
+        pick = lambda allk: [allk[(i + 1) * len(allk) // self.world] for i in range(self.world - 1)]
+        if utf8:
+            allk = sorted(b for o in objs for b in o)  # Python's order on bytes: unsigned, a proper prefix first
+            splitters = pick(allk) if allk else [b""] * (self.world - 1)
+            counts, perm = self.ctx.range_partition_utf8(k0, splitters, bool(ascending[0]))
         else:
-            splitters = np.zeros(self.world - 1, np.int64)
-        counts, perm = self.ctx.range_partition(k0, splitters, bool(ascending[0]))
+            allk = np.sort(np.concatenate(objs)) if objs else np.empty(0, np.int64)
+            splitters = np.array(pick(allk), np.int64) if len(allk) else np.zeros(self.world - 1, np.int64)
+            counts, perm = self.ctx.range_partition(_physical(self.ctx, k0), splitters, bool(ascending[0]))
         recv, _ = self._exchange_columns([self.ctx.take(c, perm) for c in cols], counts)
         p = self.ctx.sort_indices([recv[i] for i in key_idx], list(ascending))
         return [self.ctx.take(c, p) for c in recv]
