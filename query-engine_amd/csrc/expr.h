@@ -58,6 +58,20 @@ constexpr uint32_t kErrOverflow = 1u;
 constexpr uint32_t kErrDiv0 = 2u;
 constexpr uint32_t kErrModOverflow = 4u;
 constexpr uint32_t kErrSpin = 8u;
+constexpr uint32_t kErrExprMask = kErrOverflow | kErrDiv0 | kErrModOverflow;
+
+// Which expression error a launch reports: the reference's first.  evaluate_expr is post-order and
+// every operator finishes its whole array (rows in order, NULL rows skipped) before the next one
+// starts, so the first error is the minimum of (instruction, row) over the valid rows that raise --
+// compile_expr emits in postfix order, and the D_TOF64 it inserts cannot raise.  A lane keeps that
+// minimum as a key (pc < kMaxInstr, row < 2^32 by check_column, kind = one kErr* bit) and merges its
+// complement with one 64-bit atomicMax into a zeroed word, so that 0 still means "no error".
+constexpr uint64_t kNoFirstErr = ~0ull;
+__host__ __device__ inline uint64_t first_err_key(int pc, int64_t row, uint32_t kind) {
+    return ((uint64_t)pc << 35) | ((uint64_t)row << 3) | kind;
+}
+// the kErr* bit of the first error in a launch's first-error word (0: none)
+inline uint32_t first_err_kind(uint64_t word) { return word ? (uint32_t)(~word & 7u) : 0u; }
 
 // Host side --------------------------------------------------------------------
 // Compile `e` over columns of `dtypes`.  Returns QEH_OK or an error status with

@@ -149,10 +149,11 @@ __device__ __forceinline__ void load_rows(const ColRef &c, int64_t row0, int64_t
     }
 }
 
-// Run a full program over R rows; result in slot 0.  `err` collects kErr* bits.
+// Run a full program over R rows; result in slot 0.  `first` keeps the lane's least first_err_key
+// (expr.h) over its calls; it starts as kNoFirstErr.
 template <int R>
 __device__ void run_program(const DevProgram &P, const ColSet &cols, int64_t row0, int64_t stride,
-                            int64_t n, ExprRegs<R> &X, uint32_t &err) {
+                            int64_t n, ExprRegs<R> &X, uint64_t &first) {
     // rows of this call that exist: a literal is valid on those only (a program of literals alone,
     // e.g. what an EXISTS subquery becomes, must not select rows at and past n)
     uint32_t live = 0;
@@ -245,9 +246,10 @@ __device__ void run_program(const DevProgram &P, const ColSet &cols, int64_t row
                 } else {
                     // checked integer arithmetic; errors only on valid rows (arrow try_binary)
                     const bool i32 = t == QEH_DT_INT32;
+                    const uint32_t vin = vo;                      // rows valid in both operands
+                    uint32_t e_ovf = 0, e_div0 = 0, e_mod = 0;    // bit r: row r raises that error
 #pragma unroll
                     for (int r = 0; r < R; ++r) {
-                        const bool live = (vo >> r) & 1;
                         int64_t x = a[r], y = b[r], z = 0;
                         bool ov = false;
                         switch (in.op) {
@@ -255,21 +257,30 @@ __device__ void run_program(const DevProgram &P, const ColSet &cols, int64_t row
                             case D_SUB: ov = sub_ovf64(x, y, &z); break;
                             case D_MUL: ov = mul_ovf64(x, y, &z); break;
                             case D_DIV:
-                                if (y == 0) { if (live) err |= kErrDiv0; z = 0; }
+                                if (y == 0) { e_div0 |= 1u << r; z = 0; }
                                 else if (y == -1 && x == (i32 ? (int64_t)INT32_MIN : INT64_MIN)) { ov = true; z = 0; }
                                 else z = x / y;
                                 break;
                             default:  // D_MOD: r == 0 -> NULL (operators.rs:711-743)
                                 if (y == 0) { vo &= ~(1u << r); z = 0; }
                                 else if (y == -1 && x == (i32 ? (int64_t)INT32_MIN : INT64_MIN)) {
-                                    if (live) err |= kErrModOverflow;
+                                    e_mod |= 1u << r;
                                     z = 0;
                                 } else z = x % y;
                                 break;
                         }
                         if (i32 && (z < INT32_MIN || z > INT32_MAX)) ov = true;
-                        if (ov && live) err |= kErrOverflow;
+                        if (ov) e_ovf |= 1u << r;
                         o[r] = z;
+                    }
+                    const uint32_t bad = (e_ovf | e_div0 | e_mod) & vin;
+                    if (bad) {
+                        // a row raises one kind at most (the zero divisor is checked first), and the
+                        // lane's rows ascend with r: the lowest bit is its first error of this pc
+                        const int r = __builtin_ctz(bad);
+                        const uint32_t kind = ((e_div0 >> r) & 1) ? kErrDiv0 : ((e_mod >> r) & 1) ? kErrModOverflow : kErrOverflow;
+                        const uint64_t key = first_err_key(pc, row0 + r * stride, kind);
+                        if (key < first) first = key;
                     }
                 }
                 break;
@@ -277,6 +288,13 @@ __device__ void run_program(const DevProgram &P, const ColSet &cols, int64_t row
         }
         put_slot<R>(X, in.dst, o, vo);
     }
+}
+
+// A lane that saw an error (first != kNoFirstErr) reports it: its kind into the launch's error bits,
+// its key into the launch's first-error word (zeroed by the host; nullptr: kinds only).
+__device__ __forceinline__ void report_first_error(uint32_t *errp, unsigned long long *firstp, uint64_t first) {
+    atomicOr(errp, (uint32_t)(first & 7u));
+    if (firstp) atomicMax(firstp, (unsigned long long)~first);
 }
 
 // Fast predicate: returns the R-bit mask of rows whose predicate is TRUE.

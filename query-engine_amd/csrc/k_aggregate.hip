@@ -33,7 +33,8 @@ namespace qeh {
 template <int GM, int PM, bool LDS>
 __global__ __launch_bounds__(kBlock) void k_agg_rows(ColSet cols, int64_t n, PredTerms terms, DevProgram prog,
                                                      GidSource src, AggSpecs specs, int64_t G,
-                                                     uint64_t *__restrict__ gstates_all, uint32_t *__restrict__ errp) {
+                                                     uint64_t *__restrict__ gstates_all, uint32_t *__restrict__ errp,
+                                                     unsigned long long *__restrict__ firstp) {
     uint64_t *__restrict__ gstates = shard_states(gstates_all, specs, G);
     extern __shared__ __attribute__((aligned(16))) uint64_t lds[];
     uint64_t *st = LDS ? lds : gstates;
@@ -51,7 +52,7 @@ __global__ __launch_bounds__(kBlock) void k_agg_rows(ColSet cols, int64_t n, Pre
         __syncthreads();
     }
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint32_t err = 0;
+    uint64_t first = kNoFirstErr;
     const int64_t ntiles = (n + kAggTile - 1) / kAggTile;
     for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
         const int64_t row0 = tile * kAggTile + (int64_t)wave * 64 * kAggR + lane;
@@ -60,7 +61,7 @@ __global__ __launch_bounds__(kBlock) void k_agg_rows(ColSet cols, int64_t n, Pre
             sel = eval_terms<kAggR>(terms, cols, row0, 64, n);
         } else if (PM == PM_PROG) {
             ExprRegs<kAggR> X;
-            run_program<kAggR>(prog, cols, row0, 64, n, X, err);
+            run_program<kAggR>(prog, cols, row0, 64, n, X, first);
             sel = program_true_mask<kAggR>(X);
         } else {
             sel = 0;
@@ -98,7 +99,7 @@ __global__ __launch_bounds__(kBlock) void k_agg_rows(ColSet cols, int64_t n, Pre
             }
         }
     }
-    if (err) atomicOr(errp, err);
+    if (first != kNoFirstErr) report_first_error(errp, firstp, first);
     if (LDS) {
         __syncthreads();
         for (int64_t g = threadIdx.x; g < G; g += blockDim.x) {
@@ -1029,7 +1030,8 @@ __device__ __forceinline__ int64_t gt_slot(const GTable &g, int64_t key) {
 template <int PM>
 __global__ __launch_bounds__(kBlock) void k_groupby_lds(ColSet cols, int64_t n, PredTerms terms, DevProgram prog,
                                                         int key_col, GidSource src, AggSpecs specs, int64_t G,
-                                                        uint64_t *__restrict__ gstates_all, uint32_t *__restrict__ errp) {
+                                                        uint64_t *__restrict__ gstates_all, uint32_t *__restrict__ errp,
+                                                        unsigned long long *__restrict__ firstp) {
     uint64_t *__restrict__ gstates = shard_states(gstates_all, specs, G);
     extern __shared__ __attribute__((aligned(16))) uint64_t lds[];
     const int lcap = src.lcap;
@@ -1046,7 +1048,7 @@ __global__ __launch_bounds__(kBlock) void k_groupby_lds(ColSet cols, int64_t n, 
     __syncthreads();
     const int64_t gcap = (int64_t)src.gt.mask + 1;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint32_t err = 0;
+    uint64_t first = kNoFirstErr;
     const int64_t ntiles = (n + kAggTile - 1) / kAggTile;
     for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
         const int64_t row0 = tile * kAggTile + (int64_t)wave * 64 * kAggR + lane;
@@ -1055,7 +1057,7 @@ __global__ __launch_bounds__(kBlock) void k_groupby_lds(ColSet cols, int64_t n, 
             sel = eval_terms<kAggR>(terms, cols, row0, 64, n);
         } else if (PM == PM_PROG) {
             ExprRegs<kAggR> X;
-            run_program<kAggR>(prog, cols, row0, 64, n, X, err);
+            run_program<kAggR>(prog, cols, row0, 64, n, X, first);
             sel = program_true_mask<kAggR>(X);
         } else {
             sel = 0;
@@ -1115,7 +1117,7 @@ __global__ __launch_bounds__(kBlock) void k_groupby_lds(ColSet cols, int64_t n, 
             }
         }
     }
-    if (err) atomicOr(errp, err);
+    if (first != kNoFirstErr) report_first_error(errp, firstp, first);
     __syncthreads();
     for (int i = threadIdx.x; i < lcap; i += blockDim.x) {
         const int64_t key = lkeys[i];
@@ -1523,10 +1525,10 @@ static int plan_predicate(const qeh_expr *pred, const int32_t *dtypes, int n_col
 template <int GM>
 static void launch_agg_rows(qeh_ctx *ctx, int pm, bool lds, int grid, size_t shmem, const ColSet &cols, int64_t n,
                             const PredPlan &pp, const GidSource &src, const AggSpecs &specs, int64_t G,
-                            uint64_t *states, uint32_t *err) {
+                            uint64_t *states, uint32_t *err, unsigned long long *first = nullptr) {
 #define QEH_LAUNCH(PMV, LDSV)                                                                                  \
     hipLaunchKernelGGL((k_agg_rows<GM, PMV, LDSV>), dim3(grid), dim3(kBlock), shmem, ctx->stream, cols, n, pp.terms, \
-                       pp.prog, src, specs, G, states, err)
+                       pp.prog, src, specs, G, states, err, first)
     if (pm == PM_NONE) { if (lds) QEH_LAUNCH(PM_NONE, true); else QEH_LAUNCH(PM_NONE, false); }
     else if (pm == PM_TERMS) { if (lds) QEH_LAUNCH(PM_TERMS, true); else QEH_LAUNCH(PM_TERMS, false); }
     else { if (lds) QEH_LAUNCH(PM_PROG, true); else QEH_LAUNCH(PM_PROG, false); }
@@ -2234,10 +2236,10 @@ static bool lds_group_fast(qeh_ctx *ctx, const ColSet &cols, int64_t n, const Pr
         const size_t tshm = (size_t)(1 + specs.n_slots) * src.lcap * 8;
         if (pp.mode == PM_TERMS)
             hipLaunchKernelGGL(k_groupby_lds<PM_TERMS>, dim3(1), dim3(kBlock), tshm, ctx->stream, tail, n - done, pp.terms,
-                               pp.prog, src.key_col, src, specs, G, states, err);
+                               pp.prog, src.key_col, src, specs, G, states, err, nullptr);
         else
             hipLaunchKernelGGL(k_groupby_lds<PM_NONE>, dim3(1), dim3(kBlock), tshm, ctx->stream, tail, n - done, pp.terms,
-                               pp.prog, src.key_col, src, specs, G, states, err);
+                               pp.prog, src.key_col, src, specs, G, states, err, nullptr);
     }
     return true;
 }
@@ -2257,9 +2259,15 @@ static int aggregate_rows(qeh_ctx *ctx, int gm, const ColSet &cols, int64_t n, c
     while (specs.shards < 64 && (size_t)specs.n_slots * Gs * 8 * specs.shards * 2 <= (8u << 20)) specs.shards *= 2;
     if (std::getenv("QEH_NO_SHARDS")) specs.shards = 1;
     QEH_TRY(states.alloc(ctx, (size_t)specs.shards * specs.n_slots * Gs * 8));
-    // status words, read back in one go: [0] kernel error bits, [1] slice-region overflow, [2..3] groups
-    QEH_TRY(errw.alloc(ctx, 16));
-    QEH_HIP(hipMemsetAsync(errw.p, 0, 16, ctx->stream));
+    // status words, read back in one go: [0] kernel error bits, [1] slice-region overflow, [2..3] groups,
+    // [4..5] the predicate program's first-error word (expr.h)
+    constexpr size_t kStatusBytes = 24;
+    QEH_TRY(errw.alloc(ctx, kStatusBytes));
+    QEH_HIP(hipMemsetAsync(errw.p, 0, kStatusBytes, ctx->stream));
+    unsigned long long *first = (unsigned long long *)(errw.as<uint32_t>() + 4);
+    auto status_of = [](const uint32_t *stw) {
+        return kernel_error_status(stw[0], "aggregate", (uint64_t)stw[4] | ((uint64_t)stw[5] << 32));
+    };
     bool ovf_pending = false;
     hipLaunchKernelGGL(k_states_init, dim3(grid_for(ctx, specs.shards * specs.n_slots * Gs, kBlock * 4, 8)), dim3(kBlock), 0,
                        ctx->stream, states.as<uint64_t>(), Gs, specs);
@@ -2272,7 +2280,7 @@ static int aggregate_rows(qeh_ctx *ctx, int gm, const ColSet &cols, int64_t n, c
         } else if (!(lds && try_fast_join(ctx, cols, n, pp, src, specs, Gs, states.as<uint64_t>(), errw.as<uint32_t>(),
                                           lds_bytes, per_cu)))
             launch_agg_rows<GM_JOIN>(ctx, pp.mode, lds, grid, lds ? lds_bytes : 0, cols, n, pp, src, specs, Gs,
-                                     states.as<uint64_t>(), errw.as<uint32_t>());
+                                     states.as<uint64_t>(), errw.as<uint32_t>(), first);
     };
     int per_cu = lds ? (int)std::max<size_t>(1, std::min<size_t>(8, (160 * 1024) / std::max<size_t>(lds_bytes, 1))) : 8;
     per_cu = std::min(per_cu, 8);
@@ -2280,7 +2288,7 @@ static int aggregate_rows(qeh_ctx *ctx, int gm, const ColSet &cols, int64_t n, c
     if (n > 0 && G > 0) {
         // LDS partials: ~3-6 workgroups per CU; fewer per CU when the state is large (per_cu above)
         KernelTimer kt(ctx, kname);
-        if (gm == GM_ZERO) launch_agg_rows<GM_ZERO>(ctx, pp.mode, lds, grid, lds ? lds_bytes : 0, cols, n, pp, src, specs, Gs, states.as<uint64_t>(), errw.as<uint32_t>());
+        if (gm == GM_ZERO) launch_agg_rows<GM_ZERO>(ctx, pp.mode, lds, grid, lds ? lds_bytes : 0, cols, n, pp, src, specs, Gs, states.as<uint64_t>(), errw.as<uint32_t>(), first);
         else if (gm == GM_JOIN) {
             const int sj = lds ? try_slice_join(ctx, cols, n, pp, src, specs, Gs, states.as<uint64_t>(), errw.as<uint32_t>(),
                                                 lds_bytes, pre, errw.as<uint32_t>() + 1)
@@ -2298,15 +2306,15 @@ static int aggregate_rows(qeh_ctx *ctx, int gm, const ColSet &cols, int64_t n, c
             const int g2 = grid_for(ctx, n, kAggTile, pc);
             if (pp.mode == PM_TERMS)
                 hipLaunchKernelGGL(k_groupby_lds<PM_TERMS>, dim3(g2), dim3(kBlock), shm, ctx->stream, cols, n, pp.terms,
-                                   pp.prog, src.key_col, src, specs, Gs, states.as<uint64_t>(), errw.as<uint32_t>());
+                                   pp.prog, src.key_col, src, specs, Gs, states.as<uint64_t>(), errw.as<uint32_t>(), first);
             else if (pp.mode == PM_PROG)
                 hipLaunchKernelGGL(k_groupby_lds<PM_PROG>, dim3(g2), dim3(kBlock), shm, ctx->stream, cols, n, pp.terms,
-                                   pp.prog, src.key_col, src, specs, Gs, states.as<uint64_t>(), errw.as<uint32_t>());
+                                   pp.prog, src.key_col, src, specs, Gs, states.as<uint64_t>(), errw.as<uint32_t>(), first);
             else
                 hipLaunchKernelGGL(k_groupby_lds<PM_NONE>, dim3(g2), dim3(kBlock), shm, ctx->stream, cols, n, pp.terms,
-                                   pp.prog, src.key_col, src, specs, Gs, states.as<uint64_t>(), errw.as<uint32_t>());
+                                   pp.prog, src.key_col, src, specs, Gs, states.as<uint64_t>(), errw.as<uint32_t>(), first);
         }
-        else launch_agg_rows<GM_GROUP>(ctx, pp.mode, lds, grid, lds ? lds_bytes : 0, cols, n, pp, src, specs, Gs, states.as<uint64_t>(), errw.as<uint32_t>());
+        else launch_agg_rows<GM_GROUP>(ctx, pp.mode, lds, grid, lds ? lds_bytes : 0, cols, n, pp, src, specs, Gs, states.as<uint64_t>(), errw.as<uint32_t>(), first);
     }
     QEH_HIP(hipGetLastError());
     // small tables with empty groups dropped: shards folded, flagged and scanned in compact() below
@@ -2339,21 +2347,21 @@ static int aggregate_rows(qeh_ctx *ctx, int gm, const ColSet &cols, int64_t n, c
             return QEH_OK;
         }
         if (G > 0) QEH_TRY(emit(nullptr));
-        uint32_t stw[4];
-        QEH_TRY(read_small(ctx, stw, errw.p, 16));
+        uint32_t stw[6];
+        QEH_TRY(read_small(ctx, stw, errw.p, kStatusBytes));
         if (ovf_pending && stw[1]) {
             hipLaunchKernelGGL(k_states_init, dim3(grid_for(ctx, specs.shards * specs.n_slots * Gs, kBlock * 4, 8)), dim3(kBlock),
                                0, ctx->stream, states.as<uint64_t>(), Gs, specs);
-            QEH_HIP(hipMemsetAsync(errw.p, 0, 16, ctx->stream));
+            QEH_HIP(hipMemsetAsync(errw.p, 0, kStatusBytes, ctx->stream));
             {
                 KernelTimer kt(ctx, kname);
                 join_fallback(grid, per_cu);
             }
             QEH_HIP(hipGetLastError());
             if (G > 0) QEH_TRY(emit(nullptr));
-            QEH_TRY(read_small(ctx, stw, errw.p, 16));
+            QEH_TRY(read_small(ctx, stw, errw.p, kStatusBytes));
         }
-        QEH_TRY(kernel_error_status(stw[0], "aggregate"));
+        QEH_TRY(status_of(stw));
         *out_groups = G;
         return QEH_OK;
     }
@@ -2431,7 +2439,7 @@ static int aggregate_rows(qeh_ctx *ctx, int gm, const ColSet &cols, int64_t n, c
                            states.as<uint64_t>(), Gs, posp, out_keys_src, rep_row, specs, oc);
         return hipGetLastError() == hipSuccess ? QEH_OK : fail(QEH_E_HIP, "aggregate: finalize launch failed");
     };
-    uint32_t stw[4];
+    uint32_t stw[6];
     // Small group counts: the outputs are allocated for all G groups and finalized before the group
     // count is known (k_finalize writes every non-empty group at its compacted position), so the
     // status words are read once, after the last kernel -- one host round trip per call instead of two.
@@ -2439,17 +2447,17 @@ static int aggregate_rows(qeh_ctx *ctx, int gm, const ColSet &cols, int64_t n, c
     if (early) {
         QEH_TRY(make_outputs((uint64_t)Gs));
         int s = finalize();
-        if (s == QEH_OK) s = read_small(ctx, stw, errw.p, 16);  // syncs: the finalize has run
+        if (s == QEH_OK) s = read_small(ctx, stw, errw.p, kStatusBytes);  // syncs: the finalize has run
         if (s != QEH_OK || (ovf_pending && stw[1]) || stw[0]) cleanup();
         QEH_TRY(s);
     } else {
-        QEH_TRY(read_small(ctx, stw, errw.p, 16));  // one host round trip: error bits, overflow, group count
+        QEH_TRY(read_small(ctx, stw, errw.p, kStatusBytes));  // one host round trip: error bits, overflow, group count
     }
     if (ovf_pending && stw[1]) {
         // a slice region overflowed (probe keys skewed onto few slices): the single fused pass instead
         hipLaunchKernelGGL(k_states_init, dim3(grid_for(ctx, specs.shards * specs.n_slots * Gs, kBlock * 4, 8)), dim3(kBlock),
                            0, ctx->stream, states.as<uint64_t>(), Gs, specs);
-        QEH_HIP(hipMemsetAsync(errw.p, 0, 16, ctx->stream));
+        QEH_HIP(hipMemsetAsync(errw.p, 0, kStatusBytes, ctx->stream));
         {
             KernelTimer kt(ctx, kname);
             join_fallback(grid, per_cu);
@@ -2457,9 +2465,9 @@ static int aggregate_rows(qeh_ctx *ctx, int gm, const ColSet &cols, int64_t n, c
         QEH_HIP(hipGetLastError());
         reduce_shards();
         QEH_TRY(compact());
-        QEH_TRY(read_small(ctx, stw, errw.p, 16));
+        QEH_TRY(read_small(ctx, stw, errw.p, kStatusBytes));
     }
-    QEH_TRY(kernel_error_status(stw[0], "aggregate"));
+    QEH_TRY(status_of(stw));
     if (posp) out_n = (uint64_t)stw[2] | ((uint64_t)stw[3] << 32);
     if (made == 0) {  // not finalized early (large G, or re-run after an overflow)
         QEH_TRY(make_outputs(out_n));

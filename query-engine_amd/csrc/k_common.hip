@@ -52,7 +52,9 @@ int make_colset(const qeh_column *cols, int n, ColSet *out) {
     return QEH_OK;
 }
 
-int kernel_error_status(uint32_t err, const char *op) {
+int kernel_error_status(uint32_t err, const char *op, uint64_t first) {
+    // the first error of the expression program decides among the kinds the lanes saw (expr.h)
+    if (first) err = (err & ~kErrExprMask) | first_err_kind(first);
     if (err & kErrDiv0) return fail(QEH_E_DIV0, "Arrow error: Divide by zero error");
     if (err & kErrModOverflow)
         return fail(QEH_E_OVERFLOW, "attempt to calculate the remainder with overflow (the reference aborts here, operators.rs:720)");

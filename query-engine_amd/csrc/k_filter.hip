@@ -47,6 +47,7 @@ template <int PM>
 __global__ __launch_bounds__(kBlock) void k_filter(ColSet cols, int64_t n, int64_t n_tiles, PredTerms terms,
                                                    DevProgram prog, OutSpecs outs, uint64_t *__restrict__ status,
                                                    unsigned long long *__restrict__ ticket, uint32_t *__restrict__ errp,
+                                                   unsigned long long *__restrict__ firstp,
                                                    uint64_t *__restrict__ total_out, uint64_t cap, uint64_t exit_at,
                                                    uint64_t *__restrict__ done) {
     __shared__ uint32_t wave_cnt[kFR][kBlock / 64];
@@ -56,7 +57,7 @@ __global__ __launch_bounds__(kBlock) void k_filter(ColSet cols, int64_t n, int64
     __shared__ uint32_t s_total;
     __shared__ uint32_t vbits[kMaxCols + 1][kFTile / 32 + 2];  // row kMaxCols: validity staging
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint32_t err = 0;
+    uint64_t first = kNoFirstErr;
     for (;;) {
         if (threadIdx.x == 0) {
             int64_t t = (int64_t)atomicAdd(ticket, 1ull);
@@ -77,7 +78,7 @@ __global__ __launch_bounds__(kBlock) void k_filter(ColSet cols, int64_t n, int64
             sel = eval_terms<kFR>(terms, cols, row0, kBlock, n);
         } else {
             ExprRegs<kFR> X;
-            run_program<kFR>(prog, cols, row0, kBlock, n, X, err);
+            run_program<kFR>(prog, cols, row0, kBlock, n, X, first);
             sel = program_true_mask<kFR>(X);
         }
         uint32_t rank[kFR];
@@ -188,7 +189,7 @@ __global__ __launch_bounds__(kBlock) void k_filter(ColSet cols, int64_t n, int64
         }
         __syncthreads();
     }
-    if (err) atomicOr(errp, err);
+    if (first != kNoFirstErr) report_first_error(errp, firstp, first);
 }
 
 // ---- fast filter: non-null 8-byte columns, <= 2 terms ---------------------------------------
@@ -339,15 +340,16 @@ __global__ __launch_bounds__(kBlock) void k_filter_fast(FastFilterIn in, int64_t
 constexpr int kER = 4;
 template <int RT>  // result dtype class: 0 = 8-byte, 1 = 4-byte int, 2 = float32, 3 = bool
 __global__ __launch_bounds__(kBlock) void k_eval(ColSet cols, int64_t n, DevProgram prog, void *__restrict__ out,
-                                                 uint64_t *__restrict__ out_valid, uint32_t *__restrict__ errp) {
+                                                 uint64_t *__restrict__ out_valid, uint32_t *__restrict__ errp,
+                                                 unsigned long long *__restrict__ firstp) {
     const int lane = threadIdx.x & 63;
-    uint32_t err = 0;
+    uint64_t first = kNoFirstErr;
     const int64_t nchunks = (n + 64 * kER - 1) / (64 * kER);
     const int64_t wstride = (int64_t)gridDim.x * (blockDim.x / 64);
     for (int64_t w = (int64_t)blockIdx.x * (blockDim.x / 64) + (threadIdx.x >> 6); w < nchunks; w += wstride) {
         const int64_t base = w * 64 * kER;
         ExprRegs<kER> X;
-        run_program<kER>(prog, cols, base + lane, 64, n, X, err);
+        run_program<kER>(prog, cols, base + lane, 64, n, X, first);
 #pragma unroll
         for (int r = 0; r < kER; ++r) {
             const int64_t row = base + r * 64 + lane;
@@ -365,7 +367,7 @@ __global__ __launch_bounds__(kBlock) void k_eval(ColSet cols, int64_t n, DevProg
             if (lane == 0) out_valid[(base + r * 64) >> 6] = vb;
         }
     }
-    if (err) atomicOr(errp, err);
+    if (first != kNoFirstErr) report_first_error(errp, firstp, first);
 }
 
 }  // namespace qeh
@@ -509,7 +511,7 @@ static int filter_impl(qeh_ctx *ctx, const qeh_column *cols, int n_cols, const q
     uint64_t total = 0;
     if (n_tiles > 0) {
         void *scr = nullptr;
-        const size_t hdr = 256;  // ticket/err/total in one line, `done` in its own (away from the ticket atomics)
+        const size_t hdr = 256;  // ticket/err/total/first error in one line, `done` in its own (away from the ticket atomics)
         int s = scratch_zeroed(ctx, hdr + (size_t)n_tiles * 8, &scr);
         if (s != QEH_OK) {
             cleanup();
@@ -518,6 +520,7 @@ static int filter_impl(qeh_ctx *ctx, const qeh_column *cols, int n_cols, const q
         unsigned long long *ticket = (unsigned long long *)scr;
         uint32_t *err = (uint32_t *)((char *)scr + 8);
         uint64_t *tot = (uint64_t *)((char *)scr + 16);
+        unsigned long long *first = (unsigned long long *)((char *)scr + 24);
         uint64_t *done = (uint64_t *)((char *)scr + 128);
         uint64_t *status = (uint64_t *)((char *)scr + hdr);
         const int grid = grid_for(ctx, n, kFTile, 4);
@@ -536,15 +539,15 @@ static int filter_impl(qeh_ctx *ctx, const qeh_column *cols, int n_cols, const q
 #undef QEH_FF
             } else if (fast)
                 hipLaunchKernelGGL(k_filter<1>, dim3(grid), dim3(kBlock), 0, ctx->stream, cs, n, n_tiles, terms, prog, os,
-                                   status, ticket, err, tot, cap, exit_at, done);
+                                   status, ticket, err, first, tot, cap, exit_at, done);
             else
                 hipLaunchKernelGGL(k_filter<2>, dim3(grid), dim3(kBlock), 0, ctx->stream, cs, n, n_tiles, terms, prog, os,
-                                   status, ticket, err, tot, cap, exit_at, done);
+                                   status, ticket, err, first, tot, cap, exit_at, done);
         }
         QEH_HIP(hipGetLastError());
         uint64_t hdrv[17];
         s = read_small(ctx, hdrv, scr, 136);
-        if (s == QEH_OK) s = kernel_error_status((uint32_t)hdrv[1], "filter");
+        if (s == QEH_OK) s = kernel_error_status((uint32_t)hdrv[1], "filter", hdrv[3]);
         if (s != QEH_OK) {
             cleanup();
             return s;
@@ -638,26 +641,27 @@ extern "C" int qeh_eval(qeh_ctx *ctx, const qeh_column *cols, int n_cols, const 
     {
         KernelTimer kt(ctx, "eval");
         uint32_t *err = (uint32_t *)scr;
+        unsigned long long *first = (unsigned long long *)scr + 1;
         uint64_t *ov = (uint64_t *)out->validity;
         switch (physical_dtype(rt)) {
             case QEH_DT_BOOL:
-                hipLaunchKernelGGL(k_eval<3>, dim3(grid), dim3(kBlock), 0, ctx->stream, cs, n_rows, prog, out->values, ov, err);
+                hipLaunchKernelGGL(k_eval<3>, dim3(grid), dim3(kBlock), 0, ctx->stream, cs, n_rows, prog, out->values, ov, err, first);
                 break;
             case QEH_DT_INT32:
-                hipLaunchKernelGGL(k_eval<1>, dim3(grid), dim3(kBlock), 0, ctx->stream, cs, n_rows, prog, out->values, ov, err);
+                hipLaunchKernelGGL(k_eval<1>, dim3(grid), dim3(kBlock), 0, ctx->stream, cs, n_rows, prog, out->values, ov, err, first);
                 break;
             case QEH_DT_FLOAT32:
-                hipLaunchKernelGGL(k_eval<2>, dim3(grid), dim3(kBlock), 0, ctx->stream, cs, n_rows, prog, out->values, ov, err);
+                hipLaunchKernelGGL(k_eval<2>, dim3(grid), dim3(kBlock), 0, ctx->stream, cs, n_rows, prog, out->values, ov, err, first);
                 break;
             default:
-                hipLaunchKernelGGL(k_eval<0>, dim3(grid), dim3(kBlock), 0, ctx->stream, cs, n_rows, prog, out->values, ov, err);
+                hipLaunchKernelGGL(k_eval<0>, dim3(grid), dim3(kBlock), 0, ctx->stream, cs, n_rows, prog, out->values, ov, err, first);
                 break;
         }
     }
     QEH_HIP(hipGetLastError());
-    uint32_t e = 0;
-    s = read_small(ctx, &e, scr, 4);
-    if (s == QEH_OK) s = kernel_error_status(e, "eval");
+    uint64_t e[2] = {0, 0};  // error bits, first-error word
+    s = read_small(ctx, e, scr, 16);
+    if (s == QEH_OK) s = kernel_error_status((uint32_t)e[0], "eval", e[1]);
     if (s != QEH_OK) {
         qeh_column_release(ctx, out);
         return s;

@@ -253,8 +253,9 @@ int chunk_lists(qeh_ctx *ctx, const uint16_t *tag, const uint16_t *ccnt, uint64_
 // Non-zero entries of a device table of n 2-B or 4-B entries (k_build.hip; one synchronous read).
 int count_nonzero_entries(qeh_ctx *ctx, const void *table, uint64_t n, int bytes, uint64_t *out);
 
-// Error word -> status.
-int kernel_error_status(uint32_t err, const char *op);
+// Error word -> status.  `first`: the launch's first-error word where an expression program ran
+// (expr.h); it picks the expression error that is reported.
+int kernel_error_status(uint32_t err, const char *op, uint64_t first = 0);
 
 // Environment knob for forcing a table layout in tests ("direct"/"packed"/"wide").
 int forced_table_kind();
