@@ -1343,8 +1343,8 @@ int qo_window(int func, const qo_col *part, int n_part, const qo_col *order, int
                     v = r0 < r * (q + 1) ? r0 / (q + 1) + 1 : r + (r0 - r * (q + 1)) / q + 1;
                     break;
                 }
-                case 4: src = i - param >= a ? perm[i - param] : -2; break;
-                case 5: src = i + param < b ? perm[i + param] : -2; break;
+                case 4: src = param <= i - a ? perm[i - param] : -2; break;
+                case 5: src = param < b - i ? perm[i + param] : -2; break; /* i + param may overflow */
                 case 6: src = perm[a]; break;
                 case 7: src = perm[b - 1]; break;
                 default: s = err(QEH_E_UNSUPPORTED, "oracle: window function %d", func);
