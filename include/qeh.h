@@ -783,6 +783,36 @@ void qeh_host_free(void *p);
 int qeh_decode_arrow_ipc(qeh_ctx *ctx, const uint8_t *bytes, int64_t size, qeh_column *out_cols, int max_cols,
                          int *out_n_cols, char **out_names, int64_t *out_rows);
 
+/* CSV scan: the bytes of a CSV file to typed columns on the device, in place of arrow-csv in
+ * crates/query-storage/src/csv.rs:23-38 and query-pgwire/src/server.rs:127-172.
+ * The reader takes a strict dialect (DESIGN.md §4 "CSV scan") and is exact on it; everything outside
+ * it is QEH_E_UNSUPPORTED with the message "csv: row R, column C: reason" (R: 0-based data row, -1 =
+ * the header; the lowest row, within it the lowest column), and the caller's host reader then parses
+ * the file or raises its own error.  The device raises no parse error of its own.
+ *   records: ',' delimiter, '"' quote, no escape character; a record ends at \n, \r, \r\n outside
+ *     quotes or at the end of the input; records without bytes are skipped; has_header = 1 skips the
+ *     first record (its field count is still checked); every record has exactly n_cols fields.
+ *   quoting: a field is quoted iff its first byte is '"'; inside, "" is one quote and delimiters and
+ *     terminators are data; a closing quote is followed by ',', a terminator or the end of the input.
+ *     A quote inside an unquoted field, another byte after a closing quote and an unterminated quoted
+ *     field are refused.
+ *   cells: an empty field (quoted or not) is NULL for every type.  INT32 / INT64: -?[0-9]+ in range.
+ *     FLOAT64: -?([0-9]+(\.[0-9]*)?|\.[0-9]+)([eE][+-]?[0-9]+)? or nan / inf / infinity (ASCII case-
+ *     insensitive, optional '-'), the correctly rounded double (nan = 0x7ff8000000000000, -nan with
+ *     the sign bit).  BOOL: true / false, ASCII case-insensitive.  DATE32: YYYY-MM-DD, a valid date of
+ *     the years 0001-9999.  UTF8: the bytes.  No white space is trimmed, a leading '+' is refused.
+ *   the input must be valid UTF-8; a Utf8 column beyond 2^31 - 1 bytes, more than 32 columns and
+ *     FLOAT32 / DATE64 / TIMESTAMP_* columns are refused (the latter before any kernel runs).
+ * bytes: host memory (uploaded by the call) or, with bytes_on_device = 1, device memory; only read.
+ * dtypes: n_cols enum qeh_dtype values.  out_cols[n_cols]: owned columns at offset 0; validity is NULL
+ * for a column without a NULL cell, null_count is exact, NULL slots hold zeros (Utf8: empty).  On
+ * failure nothing stays allocated.  QEH_CSV_CHUNK=<bytes per thread> (read per call) sets the
+ * structure pass's geometry for tests.  With timing enabled, qeh_kernel_time("csv_float_patch")
+ * returns the host milliseconds and, as its count, the Float64 cells that were parsed on the host. */
+int qeh_scan_csv(qeh_ctx *ctx, const uint8_t *bytes, int64_t size, int bytes_on_device,
+                 int has_header, const int32_t *dtypes, int n_cols,
+                 qeh_column *out_cols, int64_t *out_rows);
+
 /* Validity bitmap <-> one byte per row (1 = valid), for moving nullable
  * columns through byte-addressed collectives (RCCL all-to-all splits are
  * row counts, not bit offsets).  Buffers are device pointers. */

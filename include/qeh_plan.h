@@ -151,6 +151,19 @@ int qeh_source_cache_stats(qeh_ctx *ctx, int64_t *entries, int64_t *bytes, int64
 /* Device bytes the cache may hold before it drops its oldest entries (default 64 GiB). */
 int qeh_source_cache_budget(qeh_ctx *ctx, int64_t bytes);
 
+/* CsvDataSource::scan (crates/query-storage/src/csv.rs:23-38) and load_csv (query-pgwire/src/
+ * server.rs:127-172) on the device: qeh_scan_csv (qeh.h) over the file's bytes, and the parsed columns
+ * installed in the scan cache under `cache_key` (non-zero) -- the entry the first query over a cached
+ * source leaves.  A later qeh_execute_plan whose Scan carries that key runs on these columns and does
+ * not look at the source's schema or batches.  A hit hands the plan the entry's field names and types
+ * and its "holds at least one batch" flag, so the entry carries them: names[n_cols] (NULL: empty
+ * names) become the fields, all nullable, and the flag is set when the file has at least one data row
+ * (arrow-csv yields no batch for none).  On any failure the cache is left as it was;
+ * QEH_E_UNSUPPORTED (the file is outside the device dialect, or larger than the cache budget) means:
+ * pass the host reader's batches with the same key, as before. */
+int qeh_source_cache_load_csv(qeh_ctx *ctx, uint64_t cache_key, const uint8_t *bytes, int64_t size, int bytes_on_device,
+                              int has_header, const int32_t *dtypes, int n_cols, const char *const *names);
+
 /* Execute `plan` on the device.  On success *out_n_batches is 0 (the
  * reference returns no batches; out_* untouched, release == NULL) or 1
  * (out_schema / out_batch hold one exported record batch, caller releases).

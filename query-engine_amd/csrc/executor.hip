@@ -1895,6 +1895,42 @@ extern "C" int qeh_execute_plan(qeh_ctx *ctx, const qeh_plan *plan, const qeh_so
     return QEH_OK;
 }
 
+// The parsed columns of a CSV file as the cache entry import_source leaves after a miss: a hit copies
+// the whole Table, so the entry carries the fields (names, types, nullable), the row count and the
+// batch flag as well as the columns.
+extern "C" int qeh_source_cache_load_csv(qeh_ctx *ctx, uint64_t cache_key, const uint8_t *bytes, int64_t size,
+                                         int bytes_on_device, int has_header, const int32_t *dtypes, int n_cols,
+                                         const char *const *names) {
+    if (!ctx || cache_key == 0 || n_cols < 1) return qeh::fail(QEH_E_INVALID, "qeh_source_cache_load_csv: bad argument");
+    qeh::DeviceGuard dg(ctx->device);
+    std::vector<qeh_column> cols((size_t)n_cols);
+    int64_t rows = 0;
+    QEH_TRY(qeh::scan_csv(ctx, bytes, size, bytes_on_device, has_header, dtypes, n_cols, cols.data(), &rows));
+    auto keep = std::make_shared<Table>();
+    for (int i = 0; i < n_cols; ++i) {
+        keep->fields.push_back({names && names[i] ? names[i] : "", dtypes[i], true});
+        keep->cols.push_back(own(ctx, cols[(size_t)i]));
+    }
+    keep->rows = rows;
+    keep->batches = rows > 0 ? 1 : 0;
+    const size_t nbytes = table_device_bytes(*keep);
+    qeh::SourceCache &sc = source_cache(ctx);
+    std::lock_guard<std::mutex> g(sc.mu);
+    if (nbytes > sc.budget) return qeh::fail(QEH_E_UNSUPPORTED, "csv: the parsed table is larger than the scan cache's budget");
+    auto it = sc.entries.find(cache_key);
+    if (it != sc.entries.end()) {  // replaced: off the books before room is made
+        sc.bytes -= it->second.bytes;
+        sc.entries.erase(it);
+    }
+    sc.evict_oldest_until(sc.budget - nbytes);
+    auto &e = sc.entries[cache_key];
+    e.table = keep;
+    e.bytes = nbytes;
+    e.stamp = ++sc.clock;
+    sc.bytes += nbytes;
+    return QEH_OK;
+}
+
 extern "C" int qeh_source_cache_evict(qeh_ctx *ctx, uint64_t cache_key) {
     if (!ctx) return qeh::fail(QEH_E_INVALID, "null context");
     if (!ctx->source_cache) return QEH_OK;

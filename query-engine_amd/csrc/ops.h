@@ -203,6 +203,10 @@ int utf8_join_encode(qeh_ctx *ctx, const qeh_column &build, const qeh_column &pr
 // `probe [NOT] IN (set)` with SQL three-valued logic (k_semi.hip, qeh_in_set): an owned BOOL column
 // of probe.length rows.  The set becomes a bitmap over its key range or a key-only hash set.
 int in_set(qeh_ctx *ctx, const qeh_column &probe, const qeh_column &set, int negated, qeh_column *out);
+// qeh_scan_csv (k_csv.hip): CSV bytes (host or device memory) to owned columns at offset 0; nothing
+// stays allocated on failure.
+int scan_csv(qeh_ctx *ctx, const uint8_t *bytes, int64_t size, int bytes_on_device, int has_header, const int32_t *dtypes,
+             int n_cols, qeh_column *out_cols, int64_t *out_rows);
 // arrow's display name of a column type, as its error messages print it (k_utf8.hip)
 const char *arrow_type_name(int dt);
 inline bool any_utf8(const qeh_column *cols, int n) {

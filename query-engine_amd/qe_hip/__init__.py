@@ -9,7 +9,7 @@ from .device import Context, DeviceColumn, agg  # noqa: F401
 from .expr import (AggregateExpr, AggregateFunction, BinaryExpr, BinaryOp, Column, Exists,  # noqa: F401
                    InSubquery, Literal, PhysicalExpr, ScalarFunction, ScalarFunctionType, ScalarSubquery, ScalarValue,
                    UnaryExpr, UnaryOp, binop, col, lit)
-from .plan import (DataSource, Filter, HashAggregate, HashJoin, IndexScan, JoinType, Limit,  # noqa: F401
+from .plan import (CsvDataSource, DataSource, Filter, HashAggregate, HashJoin, IndexScan, JoinType, Limit,  # noqa: F401
                    MemoryDataSource, Projection, QueryExecutor, Scan, Sort, SubqueryScan, Window, WindowExpr,
                    WindowFunctionType)
 from .merge import Merge, MergeStrategy, SortColumn  # noqa: F401,E402

@@ -159,6 +159,8 @@ SIGNATURES = {
     "qeh_source_cache_evict": (I, [P, C.c_uint64]),
     "qeh_source_cache_stats": (I, [P, C.POINTER(I64), C.POINTER(I64), C.POINTER(I64), C.POINTER(I64)]),
     "qeh_source_cache_budget": (I, [P, I64]),
+    "qeh_scan_csv": (I, [P, P, I64, I, I, C.POINTER(C.c_int32), I, COLP, C.POINTER(I64)]),
+    "qeh_source_cache_load_csv": (I, [P, U64, P, I64, I, I, C.POINTER(C.c_int32), I, C.POINTER(C.c_char_p)]),  # qeh_plan.h
 }
 
 _lib = None

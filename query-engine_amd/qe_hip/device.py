@@ -50,6 +50,25 @@ def dtype_of_arrow(t) -> int:
     raise TypeError(f"arrow type {t} is not supported on the device")
 
 
+def csv_bytes_of(data):
+    """(address, size, on_device, keep-alive) of a CSV input: bytes-like, a path, or a uint8 device tensor."""
+    if hasattr(data, "data_ptr") and hasattr(data, "is_cuda"):  # a torch tensor
+        if not data.is_cuda or data.dim() != 1 or data.element_size() != 1 or not data.is_contiguous():
+            raise TypeError("a CSV device tensor is one-dimensional, contiguous, of one-byte elements, on the device")
+        return C.c_void_p(data.data_ptr() if data.numel() else None), int(data.numel()), 1, data
+    if isinstance(data, str) or hasattr(data, "__fspath__"):
+        with open(data, "rb") as f:
+            data = f.read()
+    host = np.frombuffer(data, np.uint8)
+    return C.c_void_p(host.ctypes.data if host.size else None), int(host.size), 0, host
+
+
+def csv_dtypes_of(schema):
+    """The qeh dtypes of a pa.Schema as the C array qeh_scan_csv takes."""
+    dts = [dtype_of_arrow(f.type) for f in schema]
+    return (C.c_int32 * max(len(dts), 1))(*dts)
+
+
 def pack_bits(b: np.ndarray) -> np.ndarray:
     """bool[n] -> Arrow LSB-first bitmap bytes, padded to 8 bytes."""
     bits = np.packbits(np.asarray(b, dtype=bool), bitorder="little")
@@ -800,6 +819,24 @@ class Context:
         out = abi.QehColumn()
         abi.check(self.lib.qeh_encode_pg_datarows(self.h, self._cols(cols), len(cols), C.byref(out)))
         return self._wrap(out)
+
+    def scan_csv(self, data, schema, has_header: bool = True) -> List[DeviceColumn]:
+        """CSV bytes -> one device column per field of `schema` (a pa.Schema), qeh_scan_csv.  `data`:
+        a bytes-like object, a path, or a one-dimensional uint8 device tensor (read in place).
+        Input outside the device dialect raises QehError with status QEH_E_UNSUPPORTED and the
+        message "csv: row R, column C: reason": read the file on the host then."""
+        ptr, size, on_device, _keep = csv_bytes_of(data)
+        dtypes = csv_dtypes_of(schema)
+        out = (abi.QehColumn * len(dtypes))()
+        rows = C.c_int64()
+        abi.check(self.lib.qeh_scan_csv(self.h, ptr, size, on_device, 1 if has_header else 0, dtypes, len(dtypes),
+                                        out, C.byref(rows)))
+        cols = []
+        for i in range(len(dtypes)):
+            c = abi.QehColumn()
+            C.memmove(C.byref(c), C.byref(out[i]), C.sizeof(c))
+            cols.append(self._wrap(c))
+        return cols
 
     def encode_arrow_ipc(self, cols: Sequence[DeviceColumn], names: Sequence[str]) -> np.ndarray:
         """qeh_encode_arrow_ipc: the batch as an Arrow IPC stream.  Returns a uint8 numpy view of

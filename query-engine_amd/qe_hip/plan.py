@@ -132,6 +132,60 @@ class MemoryDataSource(DataSource):
         return self._schema
 
 
+class CsvDataSource(DataSource):
+    """crates/query-storage/src/csv.rs:23-38 (and the pgwire server's load_csv, server.rs:127-172): a CSV
+    file with a header under a given schema.
+
+    scan() reads the file on the host with pyarrow.csv, the stand-in for arrow-csv.  preload(ctx)
+    parses it on the device instead (qeh_source_cache_load_csv) and leaves the columns in the scan
+    cache under this source's key, so that a plan over it imports nothing; for a file outside the
+    device dialect it returns False, the cache stays as it was and the plan imports scan()'s batches
+    as for any cached source."""
+
+    def __init__(self, path, schema: pa.Schema, device_cache: bool = True, has_header: bool = True):
+        self._path = path
+        self._schema = schema
+        self._has_header = has_header
+        self._key = next(_next_cache_key) if device_cache else 0
+        self._batches = None
+
+    def cache_key(self) -> int:
+        return self._key
+
+    def schema(self):
+        return self._schema
+
+    def scan(self):
+        if self._batches is None:
+            import pyarrow.csv as pacsv
+            names = [f.name for f in self._schema]  # the schema names the columns, as in the reference
+            table = pacsv.read_csv(
+                self._path,
+                read_options=pacsv.ReadOptions(column_names=names, skip_rows=1 if self._has_header else 0),
+                parse_options=pacsv.ParseOptions(newlines_in_values=True),
+                convert_options=pacsv.ConvertOptions(
+                    column_types=self._schema, null_values=[""], strings_can_be_null=True, quoted_strings_can_be_null=True,
+                    true_values=["true", "True", "TRUE"], false_values=["false", "False", "FALSE"]))
+            self._batches = table.cast(self._schema).combine_chunks().to_batches()
+        return list(self._batches)
+
+    def preload(self, ctx) -> bool:
+        """Parse the file on the device into the scan cache.  False: the file is outside the device
+        dialect (or device_cache is off); nothing was cached."""
+        if self._key == 0:
+            return False
+        from .device import csv_bytes_of, csv_dtypes_of
+        ptr, size, on_device, _keep = csv_bytes_of(self._path)
+        dtypes = csv_dtypes_of(self._schema)
+        names = (C.c_char_p * max(len(self._schema), 1))(*[f.name.encode() for f in self._schema])
+        s = abi.load().qeh_source_cache_load_csv(ctx.h, C.c_uint64(self._key), ptr, size, on_device,
+                                                 1 if self._has_header else 0, dtypes, len(self._schema), names)
+        if s == abi.QEH_E_UNSUPPORTED:
+            return False
+        abi.check(s)
+        return True
+
+
 # ---- PhysicalPlan ------------------------------------------------------------------
 class PhysicalPlan:
     pass

@@ -33,12 +33,16 @@
   tsmatch    to_tsvector(doc) @@ to_tsquery('gpu & kernel') over 1e7 documents of about 64 bytes: the stream
              kernel against the row-per-lane kernel (QEH_NO_TS_STREAM=1), interleaved, with GB/s over the
              bytes read
+  csv        qeh_scan_csv over 1e7 rows x (Int64, Float64 as shortest repr, Utf8 of 4-12 bytes, Date32): wall and
+             kernel time with the bytes on the device and with the upload included, the share of Float64 cells
+             parsed on the host, the byte floor (the file read by each pass plus the columns written, at 8 TB/s),
+             and pyarrow.csv.read_csv of the same bytes on 16 threads (the stand-in for arrow-csv)
   cfg4leg    config 4's per-rank device leg at N = 8 (fused filter + 8-way exchange pass over 1e9
              rows, the dim shard's exchange pass, the local join of what the rank receives)
 
 Prints one JSON line per config: rows/s, ms per run, algorithmic GB/s and
 fraction of 8 TB/s, and the oracle's rows/s on a bounded sample (1 thread).
-usage: python tools/bench_configs.py [--only cfg2,cfg3,cfg5,window,filter,limit,plan,left,full,merge,encode,partition,utf8_groupby,utf8_sort,utf8_join,topk,semi,tsmatch,temporal] [--scale 1.0]
+usage: python tools/bench_configs.py [--only cfg2,cfg3,cfg5,window,filter,limit,plan,left,full,merge,encode,partition,utf8_groupby,utf8_sort,utf8_join,topk,semi,tsmatch,temporal,csv] [--scale 1.0]
 """
 import argparse
 import json
@@ -1077,6 +1081,82 @@ def cfg_temporal(ctx, scale):
           "per_output_byte_ratio": t["kernel_ns_per_output_byte"] / i["kernel_ns_per_output_byte"]})
 
 
+CSV_KERNELS = ["csv_chunks", "csv_pick", "csv_starts", "csv_fields", "csv_utf8", "scan"]
+
+
+def cfg_csv(ctx, scale):
+    """CsvDataSource::scan / load_csv on the device.  The file is generated once on the host; five timed
+    runs after a warm-up per arm, all in this process."""
+    import pyarrow as pa
+    import pyarrow.csv as pacsv
+    n = int(1e7 * scale)
+    rng = np.random.default_rng(SEED)
+    ints = rng.integers(-2**40, 2**40, n).tolist()
+    floats = (rng.standard_normal(n) * 1e3).tolist()
+    words = ["".join(chr(97 + int(c)) for c in rng.integers(0, 26, int(k))) for k in rng.integers(4, 13, 4096)]
+    widx = rng.integers(0, len(words), n).tolist()
+    dates = np.datetime_as_string(np.datetime64("1970-01-01") + rng.integers(0, 20000, n)).tolist()
+    parts = ["k,v,s,d\n"]
+    step = 1_000_000
+    for lo in range(0, n, step):
+        parts.append("".join(f"{a},{b!r},{words[w]},{d}\n" for a, b, w, d in
+                             zip(ints[lo:lo + step], floats[lo:lo + step], widx[lo:lo + step], dates[lo:lo + step])))
+    data = "".join(parts).encode()
+    del parts, ints, floats, widx, dates
+    schema = pa.schema([("k", pa.int64()), ("v", pa.float64()), ("s", pa.string()), ("d", pa.date32())])
+    dev = torch.frombuffer(bytearray(data), dtype=torch.uint8).cuda()
+    torch.cuda.synchronize()
+    sizes = {}
+
+    def run(src):
+        cols = ctx.scan_csv(src, schema)
+        sizes["utf8"] = cols[2].c.values_bytes
+        sizes["rows"] = len(cols[0])
+        for c in cols:
+            c.release()
+
+    arms = {}
+    for arm, src in (("device_bytes", dev), ("host_bytes", data)):
+        walls = []
+        run(src)
+        ctx.sync()
+        ctx.timing(True)
+        ctx.timing_reset()
+        for _ in range(5):
+            t0 = time.perf_counter()
+            run(src)
+            ctx.sync()
+            walls.append(time.perf_counter() - t0)
+        kt = {k: ctx.kernel_time(k)[0] / 5 for k in CSV_KERNELS}
+        patch_ms, patched = ctx.kernel_time("csv_float_patch")
+        ctx.timing(False)
+        arms[arm] = {"wall_ms": [w * 1e3 for w in walls], "wall_ms_median": sorted(walls)[2] * 1e3, "kernel_ms": sum(kt.values()),
+                     "kernel_split_ms": kt, "float_cells_parsed_on_host_share": patched / 5 / max(n, 1),
+                     "float_patch_host_ms": patch_ms / 5}
+    assert sizes["rows"] == n
+    pa.set_cpu_count(16)
+    opts = dict(convert_options=pacsv.ConvertOptions(column_types=schema))
+    pacsv.read_csv(pa.BufferReader(data), **opts)
+    host = []
+    for _ in range(5):
+        t0 = time.perf_counter()
+        pacsv.read_csv(pa.BufferReader(data), **opts)
+        host.append(time.perf_counter() - t0)
+    size = len(data)
+    written = n * (8 + 8 + 4 + 4) + sizes["utf8"]
+    floor_bytes = 4 * size + written  # k_csv_chunks, k_csv_starts, k_csv_fields, k_csv_utf8 each read the file
+    d = arms["device_bytes"]
+    dominant = max((k for k in CSV_KERNELS), key=lambda k: d["kernel_split_ms"][k])
+    cpu = {"value": n / sorted(host)[2], "unit": "rows/s", "cores": 16, "kind": "pyarrow.csv.read_csv, pa.set_cpu_count(16)",
+           "ms": [h * 1e3 for h in host], "GBs": size / sorted(host)[2] / 1e9}
+    line("qeh_scan_csv 1e7 x (Int64, Float64 shortest repr, Utf8 4-12 B, Date32), bytes on the device", n,
+         d["wall_ms_median"] * 1e-3, float(floor_bytes), d["kernel_ms"], dominant, cpu,
+         {"file_bytes": size, "file_GBs_wall": size / (d["wall_ms_median"] * 1e-3) / 1e9, "floor_ms_at_8TBs": floor_bytes / 8e12 * 1e3,
+          "kernel_over_floor": d["kernel_ms"] / (floor_bytes / 8e12 * 1e3), "device_bytes": d, "host_bytes": arms["host_bytes"],
+          "speedup_vs_pyarrow16_device_bytes": sorted(host)[2] * 1e3 / d["wall_ms_median"],
+          "speedup_vs_pyarrow16_with_upload": sorted(host)[2] * 1e3 / arms["host_bytes"]["wall_ms_median"]})
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--only", default="cfg2,cfg3,cfg5,filter")
@@ -1093,7 +1173,7 @@ def main():
          "merge": cfg_merge, "encode": cfg_encode, "shapes": cfg_metric_shapes, "partition": cfg_partition, "cfg3w": cfg3_wide, "window": cfg_window,
          "cfg4leg": cfg4_leg, "cfg4items": cfg4_items_leg, "cfg5leg": cfg5_leg,
          "window_lsd": cfg_window_lsd, "utf8_groupby": cfg_utf8_groupby, "utf8_sort": cfg_utf8_sort, "utf8_join": cfg_utf8_join,
-         "topk": cfg_topk, "semi": cfg_semi, "tsmatch": cfg_tsmatch, "temporal": cfg_temporal}[name](ctx, args.scale)
+         "topk": cfg_topk, "semi": cfg_semi, "tsmatch": cfg_tsmatch, "temporal": cfg_temporal, "csv": cfg_csv}[name](ctx, args.scale)
         ctx.sync()
         abi.check(ctx.lib.qeh_pool_trim(ctx.h))
     ctx.close()
